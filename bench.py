@@ -12,13 +12,20 @@ halos and 32-byte peak records over RCCL.
 
   python bench.py [--gpus N --steps K --warmup W]   # N > 1: starts its N ranks itself
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+  python bench.py --full              # + what the headline does not need: the CPU baselines,
+                                      #   the config-2 leg after a c5 run, the stages' clocks and
+                                      #   (N > 1) the exchanges' exposed waits (untimed extra steps)
+  python bench.py --dump-outputs DIR  # the last timed step's outputs as DIR/<name>.npy
   python bench.py --workload c2       # configs[1]: 2**28 samples / GPU, D = 1 (+ the sync
                                       #   stage), north_star's FIR+FFT >= 70 % HBM target
   python bench.py --workload sync     # configs[2]: 4096-sample preamble over 2**30
   python bench.py --workload pfb      # configs[3]: 64-channel PFB, 2**29 samples / GPU
   python bench.py --freq-shift 3e8    # the chain with the NCO mixer fused into the FIR
 
-Inputs are generated on the device before timing (data resident in HBM).
+Inputs are generated on the device before timing (data resident in HBM), from
+fixed seeds: the same arguments give the same inputs at every run.  A plain run
+sets up, warms up, times the steps (per-kernel HIP events ride along in them)
+and prints the result line; everything that takes work of its own is --full's.
 """
 from __future__ import annotations
 
@@ -76,6 +83,35 @@ def generate_chunk(x: torch.Tensor, g0: int, seed: int, pre: np.ndarray, k0: int
     lo, hi = max(k0, g0), min(k0 + len(pre), g0 + n)
     if lo < hi:
         x[lo - g0:hi - g0] += torch.from_numpy(pre[lo - k0:hi - k0]).to(x.device)
+
+
+DUMP_LIMIT = 1 << 22           # elements of one array that --dump-outputs keeps
+DUMP_SEED = 20250718
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: the arrays the timed path's last step left for its
+    caller, as DIR/<name>.npy (DIR/<name>.rank<r>.npy at world > 1) in float32
+    or float64; complex arrays as (n, 2) re / im pairs.  Of an array with more
+    than DUMP_LIMIT elements a sample is kept: the elements at DUMP_LIMIT
+    sorted indices drawn from default_rng(DUMP_SEED), the same at every run, so
+    two builds compare element for element (at most 32 MiB an array)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        if isinstance(t, torch.Tensor):
+            flat = t.detach().reshape(-1)
+            if flat.numel() > DUMP_LIMIT:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), DUMP_LIMIT))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            a = flat.cpu().numpy()
+        else:
+            a = np.asarray(t)
+        if np.iscomplexobj(a):
+            a = np.ascontiguousarray(a).view(a.real.dtype).reshape(-1, 2)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        suffix = f".rank{rank}" if world > 1 else ""
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
 
 
 def cpu_baseline(samples, taps, nfft, tmpl, decim=1):
@@ -362,11 +398,12 @@ def summarize_ranks(rows):
     return out
 
 
-def run_chain_leg(args, n, decim, rank, world, local, dev, steps, warmup):
+def run_chain_leg(args, n, decim, rank, world, local, dev, steps, warmup, dump=None):
     """Build the chain for n input samples per rank at decimation `decim`, fill
     it on the device, run `warmup` untimed and `steps` timed steps (barrier +
     synchronize on both sides, max over ranks) and return the elapsed time,
-    the per-stage HIP-event means and every stage against its roof."""
+    the per-stage HIP-event means and every stage against its roof.  dump: the
+    directory for the last timed step's outputs (dump_outputs)."""
     from vector_amd.shard import ChainConfig, HipBackend, StreamChain
     from vector_amd._lib import get_context
     granule = args.nfft * decim
@@ -412,6 +449,11 @@ def run_chain_leg(args, n, decim, rank, world, local, dev, steps, warmup):
     barrier()
     lib.vsig_timing_enable(h, 0)
     elapsed = t1 - t0
+    if dump:
+        # what a caller of the step holds after it: the filtered stream, its
+        # PSD frames and the global peak record (max |c|, lag, sums, n outputs)
+        dump_outputs(dump, {"filtered": chain.y, "psd": chain.sxx,
+                            "peak": np.array(chain.global_peak(), dtype=np.float64)}, rank, world)
 
     # per-kernel durations from HIP events on the launch stream
     import ctypes as C
@@ -426,11 +468,11 @@ def run_chain_leg(args, n, decim, rank, world, local, dev, steps, warmup):
         # a SIMD's registers, so its span is the FIR's; what the step pays for it
         # is not this span (ms_per_step against --no-overlap-refine)
         stages["refine_overlapped_span"] = stages.pop("refine")
-    # untimed diagnostic steps after the timed loop (the timed steps stay the
-    # single-rank path's): each stage's effective clock, and at world > 1 the
-    # exposed waits of the exchanges
+    # --full: untimed diagnostic steps after the timed loop (the timed steps stay
+    # the single-rank path's): each stage's effective clock, and at world > 1
+    # the exposed waits of the exchanges
     clocks, waits = {}, {}
-    ndiag = 0 if args.no_kernel_timing else 3
+    ndiag = 3 if (args.full and not args.no_kernel_timing) else 0
     if ndiag:
         clocks = stage_clocks(lib, h, chain.step, ndiag)
         if world > 1:
@@ -546,6 +588,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the CPU baselines, the "
+                         "config-2 leg after a c5 run, the stages' effective clocks and (N > 1) the "
+                         "exchanges' exposed waits")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64; "
+                         "a fixed seeded sample of the large ones)")
     ap.add_argument("--workload", choices=("c5", "c2", "pfb", "sync"), default="c5",
                     help="c5: the metric's full chain (default); c2: 2**28/GPU, D=1; "
                          "sync: config 3 preamble correlation over 2**30 samples; pfb: config 4")
@@ -556,9 +605,9 @@ def main():
     ap.add_argument("--nfft", type=int, default=8192)
     ap.add_argument("--template", type=int, default=4096)
     ap.add_argument("--cpu-samples", type=int, default=None,
-                    help="CPU-baseline sample (default: ~10-15 s of single-core work: "
+                    help="--full's CPU-baseline sample (default: ~10-15 s of single-core work: "
                          "2**26 samples for the chains, 2**24 for sync, 2**27 for pfb)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baselines")
     ap.add_argument("--cpu-workers", type=int, default=None,
                     help="processes for the all-cores CPU baseline (default: this process's CPU "
                          "allowance, bench.cpu_allowance, within host memory)")
@@ -573,7 +622,7 @@ def main():
     ap.add_argument("--nchan", type=int, default=64)
     ap.add_argument("--branch-taps", type=int, default=16)
     ap.add_argument("--no-c2-leg", action="store_true",
-                    help="skip the untimed-for-headline config-2 FIR+PSD leg after a c5 run")
+                    help="--full without the untimed-for-headline config-2 FIR+PSD leg after a c5 run")
     ap.add_argument("--c2-steps", type=int, default=10)
     ap.add_argument("--c2-samples", type=int, default=1 << 28)
     ap.add_argument("--launcher-selftest", default=None, help=argparse.SUPPRESS)
@@ -607,16 +656,18 @@ def main():
         n = args.samples
     else:
         n = wsamples if weak else wsamples // world
-    leg = run_chain_leg(args, n, decim, rank, world, local, dev, args.steps, args.warmup)
+    leg = run_chain_leg(args, n, decim, rank, world, local, dev, args.steps, args.warmup,
+                        dump=args.dump_outputs)
     elapsed, stages, stage_roof, check = leg["elapsed"], leg["stages"], leg["stage_roof"], leg["check"]
     roof, taps, tmpl = leg["roof"], leg["taps"], leg["tmpl"]
     N = world * n
 
-    # north_star's own FIR+FFT target is quoted at config 2 (2**28 samples,
-    # D = 1): after the headline's timed region, rank 0 runs that chain on its
-    # GPU as a single-rank leg (not part of `value`) and reports its stages
+    # --full: north_star's own FIR+FFT target is quoted at config 2 (2**28
+    # samples, D = 1): after the headline's timed region, rank 0 runs that chain
+    # on its GPU as a single-rank leg (not part of `value`) and reports its stages
     stages_c2 = None
-    if rank == 0 and args.workload == "c5" and not args.no_c2_leg and args.decim is None:
+    if (args.full and rank == 0 and args.workload == "c5" and not args.no_c2_leg
+            and args.decim is None):
         c2 = run_chain_leg(args, args.c2_samples, WORKLOADS["c2"][0], 0, 1, local, dev,
                            args.c2_steps, args.warmup)
         stages_c2 = dict(c2["stage_roof"], check=c2["check"], samples=args.c2_samples,
@@ -630,7 +681,7 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = N / (elapsed / args.steps) / 1e6
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cs = args.cpu_samples or (1 << 26)
         cpu = cpu_baseline(cs, taps, args.nfft, tmpl, decim)
         ncores, src = cpu_allowance()
@@ -721,8 +772,13 @@ def run_sync(args, world, rank, local, dev):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     lib.vsig_timing_enable(h, 0)
-    clocks = {} if args.no_kernel_timing else stage_clocks(lib, h, lambda: xc(x, "valid", peak=pk), 3)
     peak, idx, s1, s2 = dsp._read_peak(pk)
+    if args.dump_outputs:         # the peak record: max |c|, lag, sum |c|, sum |c|^2
+        dump_outputs(args.dump_outputs, {"peak": np.array([peak, idx, s1, s2], dtype=np.float64)})
+    clocks = {}
+    if args.full and not args.no_kernel_timing:
+        clocks = stage_clocks(lib, h, lambda: xc(x, "valid", peak=pk), 3)
+        peak, idx, s1, s2 = dsp._read_peak(pk)
     nout = n - L + 1
     conf = dsp._confidence(peak, s1, s2, nout, 0.5)
     tot, cnt = C.c_double(), C.c_int64()
@@ -751,7 +807,7 @@ def run_sync(args, world, rank, local, dev):
         if "xcorr" in clocks:
             stage["xcorr"]["ghz"] = clocks["xcorr"]
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import ref        # the CPU baseline leg only
         ns = args.cpu_samples or (1 << 24)
         xs = ref.synth_iq(ns, seed=99)
@@ -818,7 +874,11 @@ def run_pfb(args, world, rank, local, dev):
     t1 = time.perf_counter()
     barrier()
     lib.vsig_timing_enable(h, 0)
-    clocks = {} if args.no_kernel_timing else stage_clocks(lib, h, ch.step, 3)
+    if args.dump_outputs:         # the rank's output frames (frame-major, nframes x nchan)
+        dump_outputs(args.dump_outputs, {"frames": ch.frames()}, rank, world)
+    clocks = {}
+    if args.full and not args.no_kernel_timing:
+        clocks = stage_clocks(lib, h, ch.step, 3)
     barrier()
     elapsed = t1 - t0
     if world > 1:
@@ -853,7 +913,7 @@ def run_pfb(args, world, rank, local, dev):
         if "pfb" in clocks:
             roof["ghz"] = clocks["pfb"]
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import ref        # the CPU baseline leg only
         ns = args.cpu_samples or (1 << 27)
         xs = ref.synth_iq(ns, seed=99)

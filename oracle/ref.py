@@ -8,8 +8,8 @@ path.
 
 It restates, in plain NumPy/SciPy, the semantics of the reference's DSP
 functions (ramiyako/vector ``utils.py``, snapshot 2025-07-18).  The reference's
-arithmetic itself lives in third-party code that is *not* vendored under
-``/root/reference``: numpy 2.2.6 (``np.correlate`` -> ``multiarray.correlate2``,
+arithmetic itself lives in third-party code that is *not* vendored in the
+reference: numpy 2.2.6 (``np.correlate`` -> ``multiarray.correlate2``,
 ``np.convolve`` -> ``multiarray.correlate``, ``numpy/_core/numeric.py:693-869``)
 and scipy 1.15.3 (``scipy.signal.spectrogram`` -> ``_spectral_helper`` ->
 ``_fft_helper`` -> pocketfft, ``scipy/signal/_spectral_py.py:816-2205``).

@@ -1,8 +1,9 @@
 """Generate the golden fixtures in tests/golden/ from the REFERENCE itself.
 
-Run in the build container only (needs /root/reference, read-only):
+Needs a checkout of the reference (read-only is enough), named by VECTOR_REFERENCE:
 
-    PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg python tests/golden/make_golden.py
+    VECTOR_REFERENCE=<checkout> PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg \
+        python tests/golden/make_golden.py
 
 It imports the reference's ``utils`` module (ramiyako/vector ``utils.py``) and
 records inputs + outputs of the hot-path functions as small ``.npz`` files.
@@ -37,6 +38,8 @@ Fixture inventory (SURVEY.md §8(c) golden set G1-G5):
   wv.npz               mat2wv's SMU-WV file bytes (vector_analyzer/mat_to_wv_converter.py:7-64)
                        for a synthetic and the reference's sample_vector.mat, normalised or not
   channel.npz          filter_channel (vector_analyzer/split_channels.py:15-44)
+  mat/*.mat            six of the reference's own MAT v5 data files, copied unchanged
+                       (tests/test_formats_cpu.py: the MAT parser against scipy.io.loadmat)
 """
 from __future__ import annotations
 
@@ -49,7 +52,7 @@ import scipy.io as sio
 import scipy.signal
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
+REF = os.environ["VECTOR_REFERENCE"]
 sys.path.insert(0, os.path.join(HERE, "..", ".."))
 sys.path.insert(0, REF)
 
@@ -414,6 +417,19 @@ def gen_channel():
     save("channel.npz", **out)
 
 
+def gen_mat():
+    """The reference's own MAT v5 files in their three layouts, byte for byte
+    (data only): complex128 'Y' alone (packet_N.mat), complex128 'Y' +
+    'pre_samples' (packet_N_<kind>.mat), complex64 'Y' + 'pre_samples'
+    (sample_vector.mat)."""
+    import shutil
+    os.makedirs(os.path.join(HERE, "mat"), exist_ok=True)
+    for rel in ("data/packet_1.mat", "data/packet_1_5MHz.mat", "data/packet_2.mat",
+                "data/packet_2_chirp.mat", "data/packet_3.mat", "sample_vector.mat"):
+        shutil.copyfile(os.path.join(REF, rel), os.path.join(HERE, "mat", os.path.basename(rel)))
+        print("copied", rel)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:
         for name in sys.argv[1:]:
@@ -430,3 +446,4 @@ if __name__ == "__main__":
     gen_xcorr()
     gen_packet()
     gen_fir()
+    gen_mat()

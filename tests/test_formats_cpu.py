@@ -1,22 +1,25 @@
 """Host-side halves of the data formats (no GPU): the MAT v5 parser against
-scipy.io.loadmat on the reference's own packet / vector files (read as data,
-never executed), and the MAT writer's byte layout against scipy.io.savemat."""
-import glob
+scipy.io.loadmat on the reference's own packet / vector files (data fixtures
+under tests/golden/mat, copied unchanged), and the MAT writer's byte layout
+against scipy.io.savemat."""
 import os
 
 import numpy as np
 import pytest
 import scipy.io as sio
 
+from conftest import GOLDEN
 from vector_amd.vectors import _plane_to_np, read_mat, write_mat_vector
 
-REF = "/root/reference"
-FILES = sorted(glob.glob(os.path.join(REF, "data", "*.mat")) + glob.glob(os.path.join(REF, "*.mat")))
+# the three layouts the reference's files come in: complex128 'Y' alone,
+# complex128 'Y' + 'pre_samples', complex64 'Y' + 'pre_samples'
+FILES = ["packet_1.mat", "packet_1_5MHz.mat", "packet_2.mat", "packet_2_chirp.mat", "packet_3.mat",
+         "sample_vector.mat"]
 
 
-@pytest.mark.skipif(not FILES, reason="reference data files not present (GPU box)")
-@pytest.mark.parametrize("path", FILES[:6])
-def test_mat_parser_matches_loadmat(path):
+@pytest.mark.parametrize("name", FILES)
+def test_mat_parser_matches_loadmat(name):
+    path = os.path.join(GOLDEN, "mat", name)
     want = sio.loadmat(path, squeeze_me=True, struct_as_record=False)
     got = read_mat(path)
     for k, v in want.items():
