@@ -305,6 +305,32 @@ int vsig_planar_to_c64_dev(vsig_ctx* ctx, int32_t mi_type, const void* re, const
                            int64_t n, void* y);
 int vsig_c64_to_planar_dev(vsig_ctx* ctx, const void* x, int64_t n, float* re, float* im);
 
+/* ---- vector assembly: generate_vector's insert loop and peak normalise
+ * (unified_gui.py:1692-1791, older form main.py:214-284).
+ * vsig_vector_build_dev: out (device complex64[n], 8-byte aligned) = the
+ *   zeroed vector after  vector[a:b] += y  for every place in list order and
+ *   every instance k = 0 .. count-1 at a = start + k*period, b = a + len
+ *   (unified_gui.py:1756-1769): the same fp32 adds in the same order, numpy's
+ *   result to the bit.  places is a host array (read before the call returns);
+ *   each y is the packet as inserted (already mixed).  Every place needs
+ *   y != NULL, len >= 1, period >= 1, count >= 0, start >= 0 and, when
+ *   count >= 1, start + (count-1)*period + len <= n (the reference inserts no
+ *   cut-off instance); n <= 2^40.  Anything else: VSIG_E_INVALID before any
+ *   work is enqueued.  No places, or every count 0: out is all zeros.
+ *   maxabs_dev (may be NULL): a device float that receives
+ *   np.max(np.abs(out)) (numpy's complex64 abs; unified_gui.py:1779).
+ * vsig_normalize_c64_dev: y = x / m, m = *maxabs_dev read on the device, as
+ *   numpy divides a complex64 array by a float32 (unified_gui.py:1780-1781);
+ *   y = x when m is not > 0.  y may be x.
+ * Both enqueue on the context stream and never synchronise (capturable). */
+typedef struct vsig_packet_place {
+  const void* y;      /* device complex64[len], as inserted */
+  int64_t len, start, period, count;   /* instance k at start + k*period, k < count */
+} vsig_packet_place;
+int vsig_vector_build_dev(vsig_ctx* ctx, const vsig_packet_place* places /*host*/, int32_t nplaces,
+                          void* out, int64_t n, float* maxabs_dev /*may be NULL*/);
+int vsig_normalize_c64_dev(vsig_ctx* ctx, const void* x, int64_t n, const float* maxabs_dev, void* y);
+
 /* ---- polyphase channelizer (BASELINE config 4; no reference counterpart,
  * nearest analogue vector_analyzer/split_channels.py:15-44):
  * y[m*nchan + k] = sum_p z_m[p] e^{-2 pi j k p / nchan},

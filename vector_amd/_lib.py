@@ -27,6 +27,11 @@ class VsigError(RuntimeError):
     pass
 
 
+class VsigInvalid(VsigError, ValueError):
+    """VSIG_E_INVALID: the library refused an argument before enqueuing any
+    work (a ValueError, as numpy raises for a bad argument)."""
+
+
 class RefineFault(VsigError):
     """The exact-argmax refine faulted on the device (its watchdog fired,
     vsig.h VSIG_E_REFINE / refine status 3): the peak record is invalid.
@@ -55,6 +60,11 @@ ALLGATHER = C.CFUNCTYPE(C.c_int, P, P, P, I64, P)
 class Transport(C.Structure):
     """vsig_transport (include/vsig.h)."""
     _fields_ = [("user", P), ("sendrecv", SENDRECV), ("allgather", ALLGATHER)]
+
+
+class PacketPlace(C.Structure):
+    """vsig_packet_place (include/vsig.h)."""
+    _fields_ = [("y", P), ("len", I64), ("start", I64), ("period", I64), ("count", I64)]
 
 # name -> (restype, argtypes); every symbol include/vsig.h declares.
 SIGNATURES = {
@@ -106,6 +116,8 @@ SIGNATURES = {
     "vsig_wv_quantize_dev": (C.c_int, [P, P, I64, C.c_float, P]),
     "vsig_planar_to_c64_dev": (C.c_int, [P, I32, P, P, I64, P]),
     "vsig_c64_to_planar_dev": (C.c_int, [P, P, I64, P, P]),
+    "vsig_vector_build_dev": (C.c_int, [P, C.POINTER(PacketPlace), I32, P, I64, P]),
+    "vsig_normalize_c64_dev": (C.c_int, [P, P, I64, P, P]),
     "vsig_pfb_c64_dev": (C.c_int, [P, P, I64, P, I32, I32, P, I64]),
     "vsig_select_dev": (C.c_int, [P, I32, P, I64, C.POINTER(I64), I32, C.POINTER(C.c_double)]),
     "vsig_threshold_dev": (C.c_int, [P, I32, P, I64, C.c_double, C.POINTER(I64), C.POINTER(I64),
@@ -233,7 +245,7 @@ class Context:
             msg = self.lib.vsig_last_error(self.h).decode()
             err = self.lib.vsig_errstr(rc).decode()
             if rc == -1:
-                raise ValueError(f"{what}: {err}: {msg}")
+                raise VsigInvalid(f"{what}: {err}: {msg}")
             if rc == -4:
                 raise NotImplementedError(f"{what}: {err}: {msg}")
             if rc == -6:

@@ -1518,6 +1518,57 @@ int vsig_c64_to_planar_dev(vsig_ctx* c, const void* x, int64_t n, float* re, flo
   return VSIG_OK;
 }
 
+// ---------------------------------------------------------------- vector assembly
+int vsig_vector_build_dev(vsig_ctx* c, const vsig_packet_place* places, int32_t nplaces, void* out,
+                          int64_t n, float* maxabs_dev) {
+  if (!c || !out || (nplaces > 0 && !places)) return fail(c, VSIG_E_INVALID, "null pointer");
+  if (nplaces < 0 || n < 0) return fail(c, VSIG_E_INVALID, "need nplaces >= 0 and n >= 0");
+  if (n > (1LL << 40)) return fail(c, VSIG_E_INVALID, "n above 2^40");
+  if (reinterpret_cast<uintptr_t>(out) & 7) return fail(c, VSIG_E_INVALID, "out must be 8-byte aligned");
+  for (int32_t i = 0; i < nplaces; ++i) {
+    const vsig_packet_place& p = places[i];
+    const std::string who = "place " + std::to_string(i) + ": ";
+    if (!p.y) return fail(c, VSIG_E_INVALID, who + "null packet pointer");
+    if (reinterpret_cast<uintptr_t>(p.y) & 7) return fail(c, VSIG_E_INVALID, who + "packet must be 8-byte aligned");
+    if (p.len < 1) return fail(c, VSIG_E_INVALID, who + "len must be >= 1");
+    if (p.period < 1) return fail(c, VSIG_E_INVALID, who + "period must be >= 1");
+    if (p.count < 0) return fail(c, VSIG_E_INVALID, who + "count must be >= 0");
+    if (p.start < 0) return fail(c, VSIG_E_INVALID, who + "start must be >= 0");
+    // start + (count-1) period + len <= n without overflow
+    if (p.count >= 1 && (p.start > n || p.len > n - p.start ||
+                         p.count - 1 > (n - p.start - p.len) / p.period))
+      return fail(c, VSIG_E_INVALID, who + "an instance ends past the vector");
+  }
+  if (maxabs_dev) HIPCHK(c, hipMemsetAsync(maxabs_dev, 0, sizeof(float), c->stream));
+  if (n == 0) return VSIG_OK;
+  // successive launches of kPlacesPerLaunch descriptors keep the add order:
+  // each later one starts from what the earlier ones wrote
+  vsig::PlaceBatch pb{};
+  int launches = 0;
+  for (int32_t i = 0; i < nplaces; ++i) {
+    const vsig_packet_place& p = places[i];
+    if (p.count == 0) continue;
+    if (pb.nd == vsig::kPlacesPerLaunch) {
+      HIPCHK(c, vsig::launch_vector_build(pb, (float2*)out, n, launches > 0, nullptr, c->stream));
+      ++launches;
+      pb.nd = 0;
+    }
+    pb.d[pb.nd++] = vsig::PlaceDesc{(const float2*)p.y, p.len, p.start, p.period, p.count};
+  }
+  HIPCHK(c, vsig::launch_vector_build(pb, (float2*)out, n, launches > 0, maxabs_dev, c->stream));
+  return VSIG_OK;
+}
+
+int vsig_normalize_c64_dev(vsig_ctx* c, const void* x, int64_t n, const float* maxabs_dev, void* y) {
+  if (!c || !x || !y || !maxabs_dev) return fail(c, VSIG_E_INVALID, "null pointer");
+  if (n < 0) return fail(c, VSIG_E_INVALID, "n < 0");
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 7)
+    return fail(c, VSIG_E_INVALID, "x and y must be 8-byte aligned");
+  if (n == 0) return VSIG_OK;
+  HIPCHK(c, vsig::launch_normalize_c64((const float2*)x, n, maxabs_dev, (float2*)y, c->stream));
+  return VSIG_OK;
+}
+
 // ---------------------------------------------------------------- PFB
 int vsig_pfb_c64_dev(vsig_ctx* c, const void* x, int64_t n, const float* h, int32_t ntaps,
                      int32_t nchan, void* y, int64_t nframes) {

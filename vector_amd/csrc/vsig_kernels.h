@@ -278,6 +278,23 @@ hipError_t launch_planar_to_c64(int mi_type, const void* re, const void* im, lon
                                 hipStream_t st);
 hipError_t launch_c64_to_planar(const float2* x, long long n, float* re, float* im, hipStream_t st);
 
+// vector_build.hip: one packet's placements (instance k at start + k period,
+// k < count, every instance inside the vector) and one launch's worth of them,
+// carried in the kernel arguments.
+struct PlaceDesc {
+  const float2* y;
+  long long len, start, period, count;
+};
+constexpr int kPlacesPerLaunch = 16;
+struct PlaceBatch {
+  PlaceDesc d[kPlacesPerLaunch];
+  int nd;
+};
+hipError_t launch_vector_build(const PlaceBatch& pb, float2* out, long long n, int load,
+                               float* maxabs, hipStream_t st);
+hipError_t launch_normalize_c64(const float2* x, long long n, const float* maxabs, float2* y,
+                                hipStream_t st);
+
 // analysis.hip
 hipError_t launch_radix_hist(int dtype, const void* a, long long n, const unsigned long long* prefix,
                              const unsigned long long* mask, int nq, int shift,

@@ -8,6 +8,9 @@
   load_packet / load_packet_info / save_vector
                                utils.py:48-105, 659-670    MAT v5 planes <-> complex64
                                                            (planar_to_c64 / c64_to_planar)
+  vector_plan / build_vector   unified_gui.py:1692-1791, main.py:214-284
+                                                           vector_build + normalize_c64
+  compute_freq_ranges          utils.py:129-159            host
 
 The MAT v5 container (128-byte header, tagged data elements) and the SMU-WV
 text header are parsed / written on the host (O(1) work); sample planes move
@@ -22,6 +25,7 @@ import struct
 import time
 import zlib
 from datetime import datetime
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -31,7 +35,8 @@ from .dsp import _device_c64, _is_dev, _ptr, peak_stats
 
 __all__ = ["apply_frequency_shift", "resample_signal", "transplant_packet_in_vector", "mat2wv",
            "save_vector_wv",
-           "load_packet", "load_packet_info", "save_vector", "read_mat", "write_mat_vector"]
+           "load_packet", "load_packet_info", "save_vector", "read_mat", "write_mat_vector",
+           "VectorPlan", "vector_plan", "build_vector", "compute_freq_ranges"]
 
 
 def _as_out(t: torch.Tensor, like_dev: bool):
@@ -430,3 +435,153 @@ def save_vector(vector, output_path):
     ctx.bind_stream()
     ctx.check(ctx.lib.vsig_c64_to_planar_dev(ctx.h, _ptr(x), n, _ptr(re), _ptr(im)), "planes")
     write_mat_vector(output_path, re.cpu().numpy(), im.cpu().numpy(), 0)
+
+
+# ---------------------------------------------------------------------------
+# vector assembly — generate_vector, unified_gui.py:1692-1791 / main.py:214-284
+# ---------------------------------------------------------------------------
+_MARKER_STYLES = ["x", "o", "^", "s", "D", "P", "v", "1", "2", "3", "4"]
+_MARKER_COLORS = [f"C{i}" for i in range(10)]
+
+
+class VectorPlan(NamedTuple):
+    """Where generate_vector puts every packet: places[i] = (start_offset,
+    period_samples, count) of config i, the vector's length, and the markers
+    (time of the instance's first payload sample, freq_shift, base name,
+    marker style, marker colour) in the reference's append order."""
+    places: list
+    total_samples: int
+    markers: list
+
+
+def _mat_packet_shape(path):
+    """(samples, pre_samples) of a packet file from its MAT v5 tags alone (host)."""
+    data = read_mat(path)
+    name = _packet_var(data, path)
+    planes = data.get((name, "planes"))
+    n = int(np.prod(planes[3])) if planes is not None else int(np.asarray(data[name]).size)
+    return n, int(data.get("pre_samples", 0))
+
+
+def _base_name(cfg, idx):
+    if cfg.get("file") is not None:
+        return os.path.splitext(os.path.basename(cfg["file"]))[0]
+    return str(cfg.get("name", f"packet_{idx + 1}"))
+
+
+def _plan(configs, lengths, pres, vector_length, sample_rate) -> VectorPlan:
+    total_samples = int(vector_length * sample_rate)
+    places, markers, styles = [], [], {}
+    for idx, (cfg, n, pre) in enumerate(zip(configs, lengths, pres)):
+        name = _base_name(cfg, idx)
+        if name not in styles:
+            styles[name] = (_MARKER_STYLES[len(styles) % len(_MARKER_STYLES)],
+                            _MARKER_COLORS[len(styles) % len(_MARKER_COLORS)])
+        style, color = styles[name]
+        period_samples = int(cfg["period"] * sample_rate)
+        if period_samples <= 0:
+            raise ValueError(f"Invalid period for packet {idx + 1}")
+        start = max(0, int(round(cfg["start_time"] * sample_rate)) - pre)
+        # instances while pos + len <= total_samples (a cut-off one is not inserted)
+        count = (total_samples - n - start) // period_samples + 1 if start + n <= total_samples else 0
+        places.append((start, period_samples, count))
+        shift = cfg.get("freq_shift", 0)
+        markers.extend(((start + k * period_samples + pre) / sample_rate, shift, name, style, color)
+                       for k in range(count))
+    return VectorPlan(places, total_samples, markers)
+
+
+def _check_vector_args(configs, vector_length):
+    if not configs:
+        raise ValueError("No packets configured")
+    if not vector_length > 0:
+        raise ValueError("Vector length must be positive")
+
+
+def _resampled_len(n, cfg, sample_rate):
+    sr = cfg.get("sample_rate")
+    return n if sr is None or sr == sample_rate else int(n * (sample_rate / sr))
+
+
+def vector_plan(configs, vector_length, sample_rate) -> VectorPlan:
+    """The placement arithmetic of generate_vector (unified_gui.py:1711,
+    1748-1769), on the host: total_samples = int(vector_length * sample_rate),
+    period_samples = int(period * sample_rate), start_offset =
+    max(0, int(round(start_time * sample_rate)) - pre_samples), instances while
+    pos + len <= total_samples.  A config's packet length comes from its
+    ``length`` key, its ``signal``, or its ``file``'s MAT header (with the
+    file's pre_samples).  ValueError for what the GUI rejects: no configs,
+    vector_length <= 0, a period below one sample."""
+    configs = list(configs)
+    _check_vector_args(configs, vector_length)
+    lengths, pres = [], []
+    for cfg in configs:
+        pre = int(cfg.get("pre_samples", 0))
+        if cfg.get("length") is not None:
+            n = int(cfg["length"])
+        elif cfg.get("signal") is not None:
+            n = int(cfg["signal"].shape[0])
+        else:
+            n, pre = _mat_packet_shape(cfg["file"])
+        lengths.append(_resampled_len(n, cfg, sample_rate))
+        pres.append(pre)
+    return _plan(configs, lengths, pres, vector_length, sample_rate)
+
+
+def build_vector(configs, vector_length, sample_rate, normalize=False, device=False):
+    """generate_vector (unified_gui.py:1692-1791) up to the save: every
+    packet loaded (``file``: load_packet_info; ``signal``: an array or device
+    tensor, with ``pre_samples``), resampled when its ``sample_rate`` differs
+    (main.py:236-237), mixed by ``freq_shift`` once (the phase restarts at
+    every instance) and added into a zeroed complex64 vector every ``period``
+    seconds from ``start_time`` -- one vsig_vector_build_dev, numpy's adds in
+    numpy's order -- then divided by its peak |v| on the device when
+    ``normalize`` (left as is when the peak is 0).  Returns (vector, markers):
+    a numpy array, or with device=True the tensor in HBM, ready for
+    save_vector / save_vector_wv / create_spectrogram."""
+    configs = list(configs)
+    _check_vector_args(configs, vector_length)
+    ctx = _lib.get_context()
+    packets, pres = [], []
+    for cfg in configs:
+        if cfg.get("signal") is not None:
+            y, pre = _device_c64(cfg["signal"], ctx), int(cfg.get("pre_samples", 0))
+        else:
+            y, pre = load_packet_info(cfg["file"], device=True)
+        sr = cfg.get("sample_rate")
+        if sr is not None and sr != sample_rate:
+            y = resample_signal(y, sr, sample_rate)
+        shift = cfg.get("freq_shift", 0)
+        if shift != 0:
+            y = apply_frequency_shift(y, shift, sample_rate)
+        packets.append(y.contiguous())
+        pres.append(pre)
+    plan = _plan(configs, [int(y.shape[0]) for y in packets], pres, vector_length, sample_rate)
+    n = plan.total_samples
+    out = torch.empty(n, dtype=torch.complex64, device=f"cuda:{ctx.device}")
+    live = [(y, pl) for y, pl in zip(packets, plan.places) if y.shape[0] > 0]
+    places = (_lib.PacketPlace * max(1, len(live)))()
+    for p, (y, (start, period, count)) in zip(places, live):
+        p.y, p.len, p.start, p.period, p.count = y.data_ptr(), int(y.shape[0]), start, period, count
+    peak = torch.empty(1, dtype=torch.float32, device=out.device) if normalize and n else None
+    ctx.bind_stream()
+    if n:
+        ctx.check(ctx.lib.vsig_vector_build_dev(ctx.h, places, len(live), _ptr(out), n,
+                                                _ptr(peak) if peak is not None else None),
+                  "vector_build")
+    if peak is not None:
+        ctx.check(ctx.lib.vsig_normalize_c64_dev(ctx.h, _ptr(out), n, _ptr(peak), _ptr(out)),
+                  "normalize")
+    return (out if device else out.cpu().numpy()), plan.markers
+
+
+def compute_freq_ranges(shifts, margin=1e6):
+    """utils.py:129-159: one (min - margin, max + margin) range over the
+    shifts that are ints or floats (bools and anything else skipped), or None
+    when there are none or every shift is zero."""
+    if not shifts or all(s == 0 for s in shifts):
+        return None
+    numbers = [s for s in shifts if isinstance(s, (int, float)) and not isinstance(s, bool)]
+    if not numbers:
+        return None
+    return [(min(numbers) - margin, max(numbers) + margin)]
