@@ -99,20 +99,7 @@ __device__ __forceinline__ void tap_range(long long i, long long na, long long n
   k1 = hi < nv ? hi : nv;
 }
 
-// Shared scratch header (zeroed before select: by the fused finalize, or a memset).
-struct RefineKeys {
-  unsigned long long count;    // candidate items appended by select
-  unsigned long long lo_inv;   // ~(lowest final output an item covers)  (atomic max)
-  unsigned long long hi_p1;    // highest final output an item covers + 1 (atomic max)
-  unsigned long long status;   // 1: more candidate outputs than the opt-in cap
-  unsigned long long done;     // numpy-pass blocks finished (the last one reduces)
-  unsigned long long fault;    // sticky: a refine_fused watchdog fired.  Nothing on
-                               // the device clears it (the finalize resets status,
-                               // not this); vsig_refine_status reports status 3 and
-                               // clears it with the launch's counters.
-  unsigned long long pad[2];
-};
-static_assert(sizeof(RefineKeys) == 64, "the items follow the keys at +64 B");
+// (RefineKeys, the shared scratch header: vsig_kernels.h)
 
 struct RefineSlot { double m; long long i; };   // one per numpy-pass block
 

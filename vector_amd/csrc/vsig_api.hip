@@ -1,10 +1,12 @@
 // C-ABI layer of libvsig.so (declared in include/vsig.h): contexts, plans
 // (twiddle tables, filter / template spectra), launch geometry, host staging.
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -17,45 +19,90 @@ struct TimingRec {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
 };
 
-constexpr size_t kRefineKeysBytes = 64;   // refine.hip RefineKeys (the scratch header)
 constexpr int kClockSlots = 32;            // per-stage clock sinks (vsig_clock_*)
 
 namespace vsig {
 thread_local unsigned long long* g_clock_sink = nullptr;
 }
 
+// Owner of one device allocation (move-only; the destructor frees it).  Every
+// device pointer the contexts and handles below own is one of these.
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { release(); p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
+    return *this;
+  }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  void* data() const { return p_; }
+  size_t bytes() const { return n_; }
+  template <class T> T* as() const { return static_cast<T*>(p_); }
+  // A fresh allocation of exactly `bytes` (what it held is freed first; empty
+  // on failure).  Plans, tables and handle members, which nothing reuses.
+  hipError_t alloc(size_t bytes) {
+    release();
+    const hipError_t e = hipMalloc(&p_, bytes);
+    if (e != hipSuccess) p_ = nullptr; else n_ = bytes;
+    return e;
+  }
+  // Context scratch: at least `bytes`, grow-only, joined with a pending
+  // asynchronous refine first (join_refine) because the caller is about to
+  // reuse the buffer; VSIG_E_NOMEM / VSIG_E_HIP and empty on failure.
+  int reserve(vsig_ctx* c, size_t bytes);
+
+ private:
+  void release() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+    n_ = 0;
+  }
+  void* p_ = nullptr;
+  size_t n_ = 0;
+};
+
+// Twiddle tables are cached per context by what they are and the transform
+// they serve: its length (n < 0: an alternative plan of |n| points, the
+// convention of plan_info / tw2_info), for FourStep log2 of it.
+enum class TableKind { Pass, TwoLevel, HalfFrame, FourStep };
+struct TableKey {
+  TableKind kind;
+  long long n;
+  bool operator<(const TableKey& o) const { return kind != o.kind ? kind < o.kind : n < o.n; }
+};
+
 struct vsig_ctx {
   int device = 0;
   hipStream_t own = nullptr;
   hipStream_t stream = nullptr;
-  std::map<int, float2*> tw;             // FFT size -> device twiddle table
-  PeakPartial* partials = nullptr;       // per-block partials
+  std::map<TableKey, DevBuf> tables;     // device twiddle tables (cached_table)
+  DevBuf partials;                       // per-block partials (ensure_partials)
   long long npartials = 0;
-  PeakPartial* result = nullptr;         // scratch device result
-  void* stage[3] = {nullptr, nullptr, nullptr};  // host-API device staging
-  size_t stage_bytes[3] = {0, 0, 0};
-  void* conv[3] = {nullptr, nullptr, nullptr};   // complex128 path: c64 operands / output
-  size_t conv_bytes[3] = {0, 0, 0};
-  void* rscratch = nullptr;              // refine.hip scratch (keys first)
-  size_t rscratch_bytes = 0;
-  void* lkeys = nullptr;                 // correlator lane keys (refine column candidates)
-  size_t lkeys_bytes = 0;
-  void* vscratch = nullptr;              // numpy-order |c| of every output (exact stats)
-  size_t vscratch_bytes = 0;
-  void* sscratch = nullptr;              // np_stats buffer sums
-  size_t sscratch_bytes = 0;
+  DevBuf result;                         // scratch device result
+  DevBuf stage[3];                       // host-API device staging
+  DevBuf conv[3];                        // complex128 path: c64 operands / output
+  DevBuf rscratch;                       // refine.hip scratch (keys first)
+  DevBuf lkeys;                          // correlator lane keys (refine column candidates)
+  DevBuf vscratch;                       // numpy-order |c| of every output (exact stats)
+  DevBuf sscratch;                       // np_stats buffer sums
+  PeakPartial* parts() const { return partials.as<PeakPartial>(); }
+  // the first-level buffer of a two-level finalize, right after the partials,
+  // then the fused finalize's block counters (zero between launches)
+  PeakPartial* finalize_tmp() const { return parts() + npartials; }
+  PeakPartial* counters() const { return finalize_tmp() + vsig::kFinalizeTmp; }
   int refine = 1;                        // exact re-rank of the correlators' peak
   int refine_eps_ppm = 1000;             // fp32 candidate band (relative, ppm of max |c|)
   long long refine_cap = 0;              // opt-in limit on candidate outputs (0: none)
   long long refine_wd_us = 2000000;      // refine_fused watchdog (option "refine_watchdog_us")
   int blas_threads = 1;                  // numpy's OpenBLAS threads (its zdotu splits > 10000 terms)
   bool refine_ran = false;
-  struct Chirp { long long M; float2* c; float2* B; };
+  struct Chirp { long long M; DevBuf c, B; };
   std::map<long long, Chirp> chirps;     // Bluestein plans by length (bigfft.hip)
-  void* bigtmp = nullptr;                // four-step scratch
-  size_t bigtmp_bytes = 0;
-  void* spec[2] = {nullptr, nullptr};    // resample / channel spectra
-  size_t spec_bytes[2] = {0, 0};
+  DevBuf bigtmp;                         // four-step scratch
+  DevBuf spec[2];                        // resample / channel spectra
   std::string err;
   bool timing = false;
   std::map<std::string, TimingRec> timers;
@@ -63,29 +110,35 @@ struct vsig_ctx {
   // ev_ref recorded after it; joined (the context stream waits on ev_ref) before
   // any reuse of its scratch -- see join_refine
   int refine_async = 0;
-  hipStream_t rstream = nullptr;
-  hipEvent_t ev_corr = nullptr, ev_ref = nullptr;
-  bool refine_pending = false;           // an async refine was enqueued
-  bool refine_joined = false;            // ... and joined on refine_joined_on
-  hipStream_t refine_joined_on = nullptr;
+  struct RefineAsync {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_corr = nullptr, ev_ref = nullptr;
+    bool pending = false;                // an async refine was enqueued
+    bool joined = false;                 // ... and joined on joined_on
+    hipStream_t joined_on = nullptr;
+  } ra;
   bool clock = false;                    // per-stage clock sinks on (vsig_clock_enable)
-  unsigned long long* clkbuf = nullptr;  // kClockSlots x {shader ticks, 100 MHz ticks}
+  DevBuf clkbuf;                         // kClockSlots x {shader ticks, 100 MHz ticks}
   std::map<std::string, int> clkslot;
 };
 
+constexpr int kFirPartTaps = 8192;
 struct vsig_fir {
   vsig_ctx* ctx;
   int ntaps, decim, M;
   long long hop;
-  float2* Hs;
-  float2* G = nullptr;   // D = 4 polyphase component filters (M = 1024)
+  DevBuf Hs;
+  DevBuf G;              // D = 4 polyphase component filters (M = 1024)
   // more than kFirPartTaps taps: undecimated parts of kFirPartTaps taps each,
   // summed with their delays (fir_part_accum); z: one part's output
   std::vector<vsig_fir*> parts;
-  float2* z = nullptr;
-  size_t zbytes = 0;
+  DevBuf z;
+  // the stream may still use the buffers: wait, then the members free them
+  ~vsig_fir() {
+    (void)hipStreamSynchronize(ctx->stream);
+    for (vsig_fir* p : parts) delete p;
+  }
 };
-constexpr int kFirPartTaps = 8192;
 
 // A correlation template: L <= 8192 one spectrum of M points; longer
 // templates a spectrum per 8192-sample chunk (M = 16384), applied as a sum of
@@ -93,12 +146,14 @@ constexpr int kFirPartTaps = 8192;
 // passes none).  tmpl: the template on the device (refine pass).
 struct vsig_xcorr {
   vsig_ctx* ctx;
-  long long L;
-  int M;
-  std::vector<float2*> Ps;
-  float2* tmpl = nullptr;
-  void* cbuf = nullptr;
-  size_t cbuf_bytes = 0;
+  long long L = 0;
+  int M = 0;
+  std::vector<DevBuf> Ps;
+  DevBuf tmpl;
+  DevBuf cbuf;
+  explicit vsig_xcorr(vsig_ctx* c) : ctx(c) {}
+  // the stream may still use the spectra: wait, then the members free them
+  ~vsig_xcorr() { (void)hipStreamSynchronize(ctx->stream); }
 };
 
 namespace {
@@ -111,13 +166,14 @@ int fail(vsig_ctx* c, int code, const std::string& msg) {
 // The context stream waits for the last asynchronous refine (once per stream
 // after each refine): called before anything reuses the refine's scratch or
 // operands -- every scratch / partials / staging allocation and use below goes
-// through ensure_buf / ensure_partials / ensure_stage -- and by vsig_refine_join.
+// through DevBuf::reserve / ensure_partials -- and by vsig_refine_join.
 void join_refine(vsig_ctx* c) {
-  if (!c->refine_pending) return;
-  if (c->refine_joined && c->refine_joined_on == c->stream) return;
-  (void)hipStreamWaitEvent(c->stream, c->ev_ref, 0);
-  c->refine_joined = true;
-  c->refine_joined_on = c->stream;
+  vsig_ctx::RefineAsync& ra = c->ra;
+  if (!ra.pending) return;
+  if (ra.joined && ra.joined_on == c->stream) return;
+  (void)hipStreamWaitEvent(c->stream, ra.ev_ref, 0);
+  ra.joined = true;
+  ra.joined_on = c->stream;
 }
 
 #define HIPCHK(ctx, expr)                                                              \
@@ -128,102 +184,89 @@ void join_refine(vsig_ctx* c) {
                   std::string(#expr) + ": " + hipGetErrorString(e_));                 \
   } while (0)
 
+// The device table for `key`, built on first use: fill(h) appends its entries
+// to a host vector (or returns a status), which is uploaded and kept for the
+// context's lifetime.  A failed upload caches nothing.
+template <class Fill>
+int cached_table(vsig_ctx* c, TableKey key, const float2** out, Fill fill) {
+  auto it = c->tables.find(key);
+  if (it != c->tables.end()) { *out = it->second.as<float2>(); return VSIG_OK; }
+  std::vector<float2> h;
+  const int rc = fill(h);
+  if (rc) return rc;
+  DevBuf d;
+  HIPCHK(c, d.alloc(h.size() * sizeof(float2)));
+  HIPCHK(c, hipMemcpy(d.data(), h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
+  *out = d.as<float2>();
+  c->tables.emplace(key, std::move(d));
+  return VSIG_OK;
+}
+
+float2 cis(double a) { return make_float2((float)std::cos(a), (float)std::sin(a)); }
+
 // Twiddle table of the plan for N (see fft_engine.hpp):
 // tw[off_p + (r-1)*Ns + k] = exp(-2 pi i r k / (Ns R)), passes p >= 1.
 int get_twiddles(vsig_ctx* c, int N, const float2** out) {
-  auto it = c->tw.find(N);
-  if (it != c->tw.end()) { *out = it->second; return VSIG_OK; }
-  int R[16], np = 0;
-  if (vsig::plan_info(N, R, &np) != hipSuccess)
-    return fail(c, VSIG_E_UNSUPPORTED, "FFT size " + std::to_string(N) + " not supported");
-  // (N < 0 keys an alternative plan of |N| points)
-  std::vector<float2> h;
-  int Ns = R[0];
-  for (int p = 1; p < np; ++p) {
-    for (int r = 1; r < R[p]; ++r)
-      for (int k = 0; k < Ns; ++k) {
-        const double a = -2.0 * M_PI * (double)r * (double)k / ((double)Ns * R[p]);
-        h.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
-      }
-    Ns *= R[p];
-  }
-  if (h.empty()) h.push_back(make_float2(1.f, 0.f));
-  float2* d = nullptr;
-  HIPCHK(c, hipMalloc(&d, h.size() * sizeof(float2)));
-  HIPCHK(c, hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
-  c->tw[N] = d;
-  *out = d;
-  return VSIG_OK;
+  return cached_table(c, {TableKind::Pass, N}, out, [&](std::vector<float2>& h) {
+    int R[16], np = 0;
+    if (vsig::plan_info(N, R, &np) != hipSuccess)
+      return fail(c, VSIG_E_UNSUPPORTED, "FFT size " + std::to_string(N) + " not supported");
+    int Ns = R[0];
+    for (int p = 1; p < np; ++p) {
+      for (int r = 1; r < R[p]; ++r)
+        for (int k = 0; k < Ns; ++k)
+          h.push_back(cis(-2.0 * M_PI * (double)r * (double)k / ((double)Ns * R[p])));
+      Ns *= R[p];
+    }
+    if (h.empty()) h.push_back(make_float2(1.f, 0.f));
+    return VSIG_OK;
+  });
 }
 
-// Two-level table for plan key N (cached under key N + 2^20).
+// Two-level table for plan key N.
 int get_tw2(vsig_ctx* c, int N, const float2** out) {
-  const int key = N + (1 << 20);
-  auto it = c->tw.find(key);
-  if (it != c->tw.end()) { *out = it->second; return VSIG_OK; }
-  int S = 0, hi = 0;
-  if (vsig::tw2_info(N, &S, &hi) != hipSuccess)
-    return fail(c, VSIG_E_UNSUPPORTED, "FFT size " + std::to_string(N) + " not supported");
-  const int n = N < 0 ? -N : N;
-  std::vector<float2> h;
-  for (int i = 0; i < hi; ++i) {
-    const double a = -2.0 * M_PI * (double)i * (double)(1 << S) / (double)n;
-    h.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
-  }
-  for (int i = 0; i < (1 << S); ++i) {
-    const double a = -2.0 * M_PI * (double)i / (double)n;
-    h.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
-  }
-  float2* d = nullptr;
-  HIPCHK(c, hipMalloc(&d, h.size() * sizeof(float2)));
-  HIPCHK(c, hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
-  c->tw[key] = d;
-  *out = d;
-  return VSIG_OK;
+  return cached_table(c, {TableKind::TwoLevel, N}, out, [&](std::vector<float2>& h) {
+    int S = 0, hi = 0;
+    if (vsig::tw2_info(N, &S, &hi) != hipSuccess)
+      return fail(c, VSIG_E_UNSUPPORTED, "FFT size " + std::to_string(N) + " not supported");
+    const int n = N < 0 ? -N : N;
+    for (int i = 0; i < hi; ++i) h.push_back(cis(-2.0 * M_PI * (double)i * (double)(1 << S) / (double)n));
+    for (int i = 0; i < (1 << S); ++i) h.push_back(cis(-2.0 * M_PI * (double)i / (double)n));
+    return VSIG_OK;
+  });
 }
 
-// W_M^t for t < T (the per-thread twiddle of the half-frame correlator),
-// cached under key M + 2^21.
+// W_M^t for t < T (the per-thread twiddle of the half-frame correlator; T is
+// a function of M).
 int get_half_tw(vsig_ctx* c, int M, int T, const float2** out) {
-  const int key = M + (1 << 21);
-  auto it = c->tw.find(key);
-  if (it != c->tw.end()) { *out = it->second; return VSIG_OK; }
-  std::vector<float2> h;
-  for (int t = 0; t < T; ++t) {
-    const double a = -2.0 * M_PI * (double)t / (double)M;
-    h.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
-  }
-  float2* d = nullptr;
-  HIPCHK(c, hipMalloc(&d, h.size() * sizeof(float2)));
-  HIPCHK(c, hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
-  c->tw[key] = d;
-  *out = d;
-  return VSIG_OK;
+  return cached_table(c, {TableKind::HalfFrame, M}, out, [&](std::vector<float2>& h) {
+    for (int t = 0; t < T; ++t) h.push_back(cis(-2.0 * M_PI * (double)t / (double)M));
+    return VSIG_OK;
+  });
 }
 
 int ensure_partials(vsig_ctx* c, long long n) {
   join_refine(c);
   if (n <= c->npartials) return VSIG_OK;
-  if (c->partials) (void)hipFree(c->partials);
-  c->partials = nullptr;
   c->npartials = 0;
   long long cap = n < 4096 ? 4096 : n + n / 4;
-  // + the first-level buffer of a two-level finalize, right after the partials,
-  // and the fused finalize's block counter (zero between launches)
-  HIPCHK(c, hipMalloc(&c->partials, (cap + vsig::kFinalizeTmp + vsig::kCounterRecs) * sizeof(PeakPartial)));
-  HIPCHK(c, hipMemset(c->partials + cap + vsig::kFinalizeTmp, 0, vsig::kCounterRecs * sizeof(PeakPartial)));
+  // + finalize_tmp() and counters() (see vsig_ctx)
+  HIPCHK(c, c->partials.alloc((cap + vsig::kFinalizeTmp + vsig::kCounterRecs) * sizeof(PeakPartial)));
+  HIPCHK(c, hipMemset(c->parts() + cap + vsig::kFinalizeTmp, 0, vsig::kCounterRecs * sizeof(PeakPartial)));
   c->npartials = cap;
   return VSIG_OK;
 }
 
-int ensure_stage(vsig_ctx* c, int i, size_t bytes) {
-  join_refine(c);
-  if (bytes <= c->stage_bytes[i]) return VSIG_OK;
-  if (c->stage[i]) (void)hipFree(c->stage[i]);
-  c->stage[i] = nullptr;
-  c->stage_bytes[i] = 0;
-  HIPCHK(c, hipMalloc(&c->stage[i], bytes));
-  c->stage_bytes[i] = bytes;
+// Host-pointer entry points: the operand into staging buffer i ...
+int stage_in(vsig_ctx* c, int i, const void* host, size_t bytes) {
+  const int rc = c->stage[i].reserve(c, bytes);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->stage[i].data(), host, bytes, hipMemcpyHostToDevice, c->stream));
+  return VSIG_OK;
+}
+// ... and a result back from the device (the caller synchronises once).
+int stage_out(vsig_ctx* c, void* host, const DevBuf& src, size_t bytes) {
+  HIPCHK(c, hipMemcpyAsync(host, src.data(), bytes, hipMemcpyDeviceToHost, c->stream));
   return VSIG_OK;
 }
 
@@ -237,12 +280,12 @@ struct Timed {
   hipStream_t st;
   Timed(vsig_ctx* c_, const char* n, hipStream_t s = nullptr)
       : c(c_), name(n), prev_sink(vsig::g_clock_sink), st(s ? s : c_->stream) {
-    if (c->clock && c->clkbuf) {
+    if (c->clock && c->clkbuf.data()) {
       auto it = c->clkslot.find(name);
       int slot = -1;
       if (it != c->clkslot.end()) slot = it->second;
       else if ((int)c->clkslot.size() < kClockSlots) slot = c->clkslot[name] = (int)c->clkslot.size();
-      if (slot >= 0) vsig::g_clock_sink = c->clkbuf + 2 * slot;
+      if (slot >= 0) vsig::g_clock_sink = c->clkbuf.as<unsigned long long>() + 2 * slot;
     }
     if (!c->timing) return;
     if (hipEventCreate(&b) != hipSuccess || hipEventCreate(&e) != hipSuccess) { b = e = nullptr; return; }
@@ -278,44 +321,72 @@ int os_size_xcorr(long long L) {
   return 0;
 }
 
-int ensure_buf(vsig_ctx* c, void** buf, size_t* have, size_t bytes) {
-  join_refine(c);
-  if (bytes <= *have) return VSIG_OK;
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr;
-  *have = 0;
-  HIPCHK(c, hipMalloc(buf, bytes));
-  *have = bytes;
-  return VSIG_OK;
-}
-
 // FFT_M(zero-padded u[0..len)) / M into a new device buffer (natural order;
 // M > 16384 by the four-step passes of bigfft.hip).
 int big_plan_fwd(vsig_ctx* c, long long M, const float2* u, long long len, float2* S);
-int make_spectrum(vsig_ctx* c, const float2* u_dev, int len, int M, float2** out) {
-  float2* S = nullptr;
-  HIPCHK(c, hipMalloc(&S, (size_t)M * sizeof(float2)));
+int make_spectrum(vsig_ctx* c, const float2* u_dev, int len, int M, DevBuf* out) {
+  DevBuf S;
+  HIPCHK(c, S.alloc((size_t)M * sizeof(float2)));
   if (M > 16384) {
-    const int rc = big_plan_fwd(c, M, u_dev, len, S);
-    if (rc) { (void)hipFree(S); return rc; }
-    *out = S;
-    return VSIG_OK;
+    const int rc = big_plan_fwd(c, M, u_dev, len, S.as<float2>());
+    if (rc) return rc;
+  } else {
+    const float2* tw;
+    const int rc = get_twiddles(c, M, &tw);
+    if (rc) return rc;
+    hipError_t e = vsig::launch_spectrum_prep(M, u_dev, len, 1.0f / (float)M, S.as<float2>(), tw, c->stream);
+    if (e != hipSuccess) return fail(c, VSIG_E_HIP, hipGetErrorString(e));
   }
-  const float2* tw;
-  int rc = get_twiddles(c, M, &tw);
-  if (rc) { (void)hipFree(S); return rc; }
-  hipError_t e = vsig::launch_spectrum_prep(M, u_dev, len, 1.0f / (float)M, S, tw, c->stream);
-  if (e != hipSuccess) { (void)hipFree(S); return fail(c, VSIG_E_HIP, hipGetErrorString(e)); }
-  *out = S;
+  *out = std::move(S);
   return VSIG_OK;
 }
 
+// Where a peak record goes: the caller's device record, or the context's.
+PeakPartial* peak_record(vsig_ctx* c, vsig_peak_t* peak_dev) {
+  return peak_dev ? reinterpret_cast<PeakPartial*>(peak_dev) : c->result.as<PeakPartial>();
+}
+
 int finalize_peak(vsig_ctx* c, long long nparts, int sqrt_max, vsig_peak_t* peak_dev) {
-  PeakPartial* dst = peak_dev ? reinterpret_cast<PeakPartial*>(peak_dev) : c->result;
-  HIPCHK(c, vsig::launch_partial_finalize(c->partials, nparts, sqrt_max, dst,
-                                          c->partials + c->npartials, c->stream));
+  HIPCHK(c, vsig::launch_partial_finalize(c->parts(), nparts, sqrt_max, peak_record(c, peak_dev),
+                                          c->finalize_tmp(), c->stream));
   return VSIG_OK;
 }
+
+// The refine scratch's header (vsig::RefineKeys), read back once the stream
+// has drained.
+int read_refine_keys(vsig_ctx* c, vsig::RefineKeys* keys) {
+  HIPCHK(c, hipMemcpyAsync(keys, c->rscratch.data(), sizeof(*keys), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VSIG_OK;
+}
+
+// After a watchdog fire: zero the keys and the fused launch's counters (a fire
+// can leave them inconsistent, and the next launch must start from zero),
+// leave `fault` in the sticky fault word, and wait for the stream.
+int clear_refine_fault(vsig_ctx* c, unsigned long long fault = 0) {
+  char* keys = c->rscratch.as<char>();
+  HIPCHK(c, hipMemsetAsync(keys, 0, sizeof(vsig::RefineKeys), c->stream));
+  if (fault)
+    HIPCHK(c, hipMemcpyAsync(keys + offsetof(vsig::RefineKeys, fault), &fault, sizeof(fault),
+                             hipMemcpyHostToDevice, c->stream));
+  if (c->parts())
+    HIPCHK(c, hipMemsetAsync(c->counters(), 0, vsig::kCounterRecs * sizeof(PeakPartial), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // also: fault is a host local
+  return VSIG_OK;
+}
+
+// np.correlate(a, v, mode): F, the start index into the 'full' correlation,
+// and the output length (numeric.py); false for an unknown mode.
+bool corr_span(int mode, long long na, long long nv, long long* F, long long* nout) {
+  const long long nmin = na < nv ? na : nv, nmax = na < nv ? nv : na;
+  if (mode == VSIG_MODE_FULL) { *F = 0; *nout = na + nv - 1; }
+  else if (mode == VSIG_MODE_VALID) { *F = nmin - 1; *nout = nmax - nmin + 1; }
+  else if (mode == VSIG_MODE_SAME) { *F = na >= nv ? nmin - 1 - nmin / 2 : nmin / 2; *nout = nmax; }
+  else return false;
+  return true;
+}
+
+bool is_complex_dtype(int dtype) { return dtype == VSIG_DTYPE_C64 || dtype == VSIG_DTYPE_C128; }
 
 // Operands of the refine pass: np.correlate(a, v) in the final output
 // space (o <-> full index F + o), complex128 or complex64 on the device.
@@ -347,12 +418,12 @@ int run_refine(vsig_ctx* c, const RefineOperands& op, long long nout, int M, lon
     int waves, Q, stride, plan, wstep, rsub;
     if (vsig::xcorr_geom(M, &waves, &Q, &stride, &plan, &wstep, &rsub) != hipSuccess)
       return fail(c, VSIG_E_INVALID, "refine: no correlator geometry for M");
-    r.parts = c->partials; r.nparts = nparts; r.hop = hop;
+    r.parts = c->parts(); r.nparts = nparts; r.hop = hop;
     r.waves = waves; r.Q = Q; r.stride = stride; r.wstep = wstep; r.rsub = rsub;
     if (fused) {
       r.finalize = 1;
-      r.tmp = c->partials + c->npartials;
-      r.done = reinterpret_cast<unsigned long long*>(r.tmp + vsig::kFinalizeTmp);
+      r.tmp = c->finalize_tmp();
+      r.done = reinterpret_cast<unsigned long long*>(c->counters());
     }
     if (lkeys) {                 // items = thread columns of Q rows, one unit each
       r.cols = Q; r.lkeys = lkeys; r.Q = 1;
@@ -363,46 +434,43 @@ int run_refine(vsig_ctx* c, const RefineOperands& op, long long nout, int M, lon
   r.cap = c->refine_cap;
   r.wd_ticks = (unsigned long long)c->refine_wd_us * 100ull;   // s_memrealtime: 100 MHz
   const size_t need = vsig::refine_scratch_bytes(r);
-  const bool fresh = need > c->rscratch_bytes;
+  const bool fresh = need > c->rscratch.bytes();
   // a watchdog fire of an earlier pass whose status nobody read (device-tensor
   // callers) lives in the old scratch's sticky fault word: carry it into the
   // new one, so vsig_refine_status still reports 3 ("fired in some pass since
   // the last call"), and clear the fused launch's counters as that report
   // does (a fire can leave them inconsistent)
   unsigned long long pending_fault = 0;
-  if (fresh && c->rscratch) {
-    unsigned long long keys[6];      // refine.hip RefineKeys: ..., fault
-    HIPCHK(c, hipMemcpyAsync(keys, c->rscratch, sizeof(keys), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    pending_fault = keys[5];
+  if (fresh && c->rscratch.data()) {
+    vsig::RefineKeys keys;
+    int rc = read_refine_keys(c, &keys);
+    if (rc) return rc;
+    pending_fault = keys.fault;
   }
-  int rc = ensure_buf(c, &c->rscratch, &c->rscratch_bytes, need);
+  int rc = c->rscratch.reserve(c, need);
   if (rc) return rc;
   // a new scratch starts with zero keys (the sticky fault word is read by
   // vsig_refine_status; the finalize resets only the per-launch words)
-  if (fresh) HIPCHK(c, hipMemsetAsync(c->rscratch, 0, kRefineKeysBytes, c->stream));
   if (pending_fault) {
-    HIPCHK(c, hipMemcpyAsync(static_cast<unsigned long long*>(c->rscratch) + 5, &pending_fault,
-                             sizeof(pending_fault), hipMemcpyHostToDevice, c->stream));
-    if (c->partials)
-      HIPCHK(c, hipMemsetAsync(c->partials + c->npartials + vsig::kFinalizeTmp, 0,
-                               vsig::kCounterRecs * sizeof(PeakPartial), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));     // pending_fault is a host local
+    if ((rc = clear_refine_fault(c, pending_fault))) return rc;
+  } else if (fresh) {
+    HIPCHK(c, hipMemsetAsync(c->rscratch.data(), 0, sizeof(vsig::RefineKeys), c->stream));
   }
-  r.scratch = c->rscratch;
+  r.scratch = c->rscratch.data();
   r.rec = rec;
   r.out128 = out128;
   if (async && c->refine_async) {
     // on the refine stream behind the correlator; ev_ref marks its end
-    HIPCHK(c, hipEventRecord(c->ev_corr, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->rstream, c->ev_corr, 0));
+    vsig_ctx::RefineAsync& ra = c->ra;
+    HIPCHK(c, hipEventRecord(ra.ev_corr, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(ra.stream, ra.ev_corr, 0));
     {
-      Timed t(c, "refine", c->rstream);
-      HIPCHK(c, vsig::launch_refine(r, c->rstream));
+      Timed t(c, "refine", ra.stream);
+      HIPCHK(c, vsig::launch_refine(r, ra.stream));
     }
-    HIPCHK(c, hipEventRecord(c->ev_ref, c->rstream));
-    c->refine_pending = true;
-    c->refine_joined = false;
+    HIPCHK(c, hipEventRecord(ra.ev_ref, ra.stream));
+    ra.pending = true;
+    ra.joined = false;
     c->refine_ran = true;
     return VSIG_OK;
   }
@@ -419,24 +487,12 @@ int get_tw_big(vsig_ctx* c, long long M, const float2** out, int* S, int* hiA) {
   while ((1LL << lg) < M) ++lg;
   *S = (lg + 1) / 2;
   *hiA = (int)(M >> *S);
-  const int key = (1 << 22) + lg;
-  auto it = c->tw.find(key);
-  if (it != c->tw.end()) { *out = it->second; return VSIG_OK; }
-  std::vector<float2> h;
-  for (long long i = 0; i < *hiA; ++i) {
-    const double a = -2.0 * M_PI * (double)(i << *S) / (double)M;
-    h.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
-  }
-  for (long long j = 0; j < (1LL << *S); ++j) {
-    const double a = -2.0 * M_PI * (double)j / (double)M;
-    h.push_back(make_float2((float)std::cos(a), (float)std::sin(a)));
-  }
-  float2* d = nullptr;
-  HIPCHK(c, hipMalloc(&d, h.size() * sizeof(float2)));
-  HIPCHK(c, hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
-  c->tw[key] = d;
-  *out = d;
-  return VSIG_OK;
+  // keyed by log2 M (every caller's M is a power of two)
+  return cached_table(c, {TableKind::FourStep, lg}, out, [&](std::vector<float2>& h) {
+    for (long long i = 0; i < *hiA; ++i) h.push_back(cis(-2.0 * M_PI * (double)(i << *S) / (double)M));
+    for (long long j = 0; j < (1LL << *S); ++j) h.push_back(cis(-2.0 * M_PI * (double)j / (double)M));
+    return VSIG_OK;
+  });
 }
 
 constexpr long long kBigMax = 1LL << 28;    // largest four-step transform
@@ -478,11 +534,11 @@ int big_plan_fwd(vsig_ctx* c, long long M, const float2* u, long long len, float
   BigPlan bp;
   int rc = big_plan(c, M, &bp);
   if (rc) return rc;
-  if ((rc = ensure_buf(c, &c->bigtmp, &c->bigtmp_bytes, (size_t)M * sizeof(float2)))) return rc;
+  if ((rc = c->bigtmp.reserve(c, (size_t)M * sizeof(float2)))) return rc;
+  float2* tmp = c->bigtmp.as<float2>();
   vsig::BigIn in{u, 0, 0, 1, len, nullptr, nullptr, 0, 1.0f / (float)M};
-  HIPCHK(c, vsig::launch_bf_col(bp.N1, bp.N2, 1, in, (float2*)c->bigtmp, bp.tw1, bp.t2, bp.S, bp.hiA,
-                                c->stream));
-  HIPCHK(c, vsig::launch_bf_row(3, bp.N1, bp.N2, 1, (float2*)c->bigtmp, nullptr, bp.tw2, 1.0f,
+  HIPCHK(c, vsig::launch_bf_col(bp.N1, bp.N2, 1, in, tmp, bp.tw1, bp.t2, bp.S, bp.hiA, c->stream));
+  HIPCHK(c, vsig::launch_bf_row(3, bp.N1, bp.N2, 1, tmp, nullptr, bp.tw2, 1.0f,
                                 reinterpret_cast<float*>(S), 0, c->stream));
   return VSIG_OK;
 }
@@ -498,15 +554,13 @@ int chirp_plan(vsig_ctx* c, long long N, vsig_ctx::Chirp** out) {
   BigPlan bp;
   int rc = big_plan(c, M, &bp);
   if (rc) return rc;
-  float2 *cv = nullptr, *B = nullptr, *b = nullptr;
-  auto cleanup = [&]() { if (cv) (void)hipFree(cv); if (B) (void)hipFree(B); if (b) (void)hipFree(b); };
-  if (hipMalloc(&cv, N * sizeof(float2)) != hipSuccess || hipMalloc(&B, M * sizeof(float2)) != hipSuccess ||
-      hipMalloc(&b, M * sizeof(float2)) != hipSuccess) {
-    cleanup();
+  DevBuf cv, Bk, b;      // b: the chirp filter before its transform, dropped on return
+  if (cv.alloc(N * sizeof(float2)) != hipSuccess || Bk.alloc(M * sizeof(float2)) != hipSuccess ||
+      b.alloc(M * sizeof(float2)) != hipSuccess)
     return fail(c, VSIG_E_NOMEM, "Bluestein plan allocation");
-  }
-  hipError_t e = vsig::launch_bf_chirp(N, M, cv, b, c->stream);
-  vsig::BigIn in{b, 0, 0, 1, M, nullptr, nullptr, 0, 1.0f / (float)M};
+  float2* B = Bk.as<float2>();
+  hipError_t e = vsig::launch_bf_chirp(N, M, cv.as<float2>(), b.as<float2>(), c->stream);
+  vsig::BigIn in{b.data(), 0, 0, 1, M, nullptr, nullptr, 0, 1.0f / (float)M};
   if (e == hipSuccess) {
     if (bp.N1 == 1) {
       vsig::BigOut o{B, 0, 0, M, nullptr, 0, 1.0f};
@@ -518,11 +572,9 @@ int chirp_plan(vsig_ctx* c, long long N, vsig_ctx::Chirp** out) {
     }
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(b);
-  b = nullptr;
-  if (e != hipSuccess) { cleanup(); return fail(c, VSIG_E_HIP, hipGetErrorString(e)); }
+  if (e != hipSuccess) return fail(c, VSIG_E_HIP, hipGetErrorString(e));
   auto& ch = c->chirps[N];
-  ch = vsig_ctx::Chirp{M, cv, B};
+  ch = vsig_ctx::Chirp{M, std::move(cv), std::move(Bk)};
   *out = &ch;
   return VSIG_OK;
 }
@@ -536,24 +588,32 @@ int dft_any(vsig_ctx* c, long long N, long long batch, vsig::BigIn in, vsig::Big
   if (rc) return rc;
   BigPlan bp;
   if ((rc = big_plan(c, ch->M, &bp))) return rc;
-  in.chirp = ch->c;
+  const float2* B = ch->B.as<float2>();
+  in.chirp = ch->c.as<float2>();
   in.conj = inverse ? 1 : 0;
   in.nvalid = in.nvalid < N ? in.nvalid : N;
-  out.chirp = ch->c;
+  out.chirp = ch->c.as<float2>();
   out.conj = inverse ? 1 : 0;
   if (bp.N1 == 1) {
-    HIPCHK(c, vsig::launch_bf_small(0, (int)ch->M, batch, in, out, ch->B, bp.tw2, c->stream));
+    HIPCHK(c, vsig::launch_bf_small(0, (int)ch->M, batch, in, out, B, bp.tw2, c->stream));
     return VSIG_OK;
   }
-  if ((rc = ensure_buf(c, &c->bigtmp, &c->bigtmp_bytes, (size_t)(batch * ch->M) * sizeof(float2)))) return rc;
-  float2* tmp = static_cast<float2*>(c->bigtmp);
+  if ((rc = c->bigtmp.reserve(c, (size_t)(batch * ch->M) * sizeof(float2)))) return rc;
+  float2* tmp = c->bigtmp.as<float2>();
   HIPCHK(c, vsig::launch_bf_col(bp.N1, bp.N2, batch, in, tmp, bp.tw1, bp.t2, bp.S, bp.hiA, c->stream));
-  HIPCHK(c, vsig::launch_bf_row(0, bp.N1, bp.N2, batch, tmp, ch->B, bp.tw2, 1.0f, nullptr, 0, c->stream));
+  HIPCHK(c, vsig::launch_bf_row(0, bp.N1, bp.N2, batch, tmp, B, bp.tw2, 1.0f, nullptr, 0, c->stream));
   HIPCHK(c, vsig::launch_bf_icol(bp.N1, bp.N2, batch, tmp, out, bp.tw1, bp.t2, bp.S, bp.hiA, c->stream));
   return VSIG_OK;
 }
 
 }  // namespace
+
+int DevBuf::reserve(vsig_ctx* c, size_t bytes) {
+  join_refine(c);
+  if (bytes <= n_) return VSIG_OK;
+  HIPCHK(c, alloc(bytes));
+  return VSIG_OK;
+}
 
 extern "C" {
 
@@ -587,7 +647,7 @@ int vsig_init(int device, vsig_ctx** out) {
   c->device = device;
   if (hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking) != hipSuccess) { delete c; return VSIG_E_HIP; }
   c->stream = c->own;
-  if (hipMalloc(&c->result, sizeof(PeakPartial)) != hipSuccess) { vsig_free(c); return VSIG_E_NOMEM; }
+  if (c->result.alloc(sizeof(PeakPartial)) != hipSuccess) { vsig_free(c); return VSIG_E_NOMEM; }
   *out = c;
   return VSIG_OK;
 }
@@ -605,24 +665,15 @@ void vsig_free(vsig_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
   vsig_timing_reset(c);
-  for (auto& kv : c->tw) (void)hipFree(kv.second);
-  if (c->partials) (void)hipFree(c->partials);
-  if (c->result) (void)hipFree(c->result);
-  for (int i = 0; i < 3; ++i) if (c->stage[i]) (void)hipFree(c->stage[i]);
-  for (int i = 0; i < 3; ++i) if (c->conv[i]) (void)hipFree(c->conv[i]);
-  if (c->rscratch) (void)hipFree(c->rscratch);
-  if (c->lkeys) (void)hipFree(c->lkeys);
-  if (c->vscratch) (void)hipFree(c->vscratch);
-  if (c->sscratch) (void)hipFree(c->sscratch);
-  for (auto& kv : c->chirps) { (void)hipFree(kv.second.c); (void)hipFree(kv.second.B); }
-  if (c->bigtmp) (void)hipFree(c->bigtmp);
-  for (int i = 0; i < 2; ++i) if (c->spec[i]) (void)hipFree(c->spec[i]);
-  if (c->clkbuf) (void)hipFree(c->clkbuf);
-  if (c->rstream) (void)hipStreamDestroy(c->rstream);
-  if (c->ev_corr) (void)hipEventDestroy(c->ev_corr);
-  if (c->ev_ref) (void)hipEventDestroy(c->ev_ref);
-  if (c->own) (void)hipStreamDestroy(c->own);
+  // the device is idle: every DevBuf of the context is freed with it, then
+  // the streams and events
+  const vsig_ctx::RefineAsync ra = c->ra;
+  const hipStream_t own = c->own;
   delete c;
+  if (ra.stream) (void)hipStreamDestroy(ra.stream);
+  if (ra.ev_corr) (void)hipEventDestroy(ra.ev_corr);
+  if (ra.ev_ref) (void)hipEventDestroy(ra.ev_ref);
+  if (own) (void)hipStreamDestroy(own);
 }
 
 const char* vsig_last_error(const vsig_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -653,15 +704,16 @@ int vsig_set_option(vsig_ctx* c, const char* key, int value) {
     if (value < 1 || value > 1024) return fail(c, VSIG_E_INVALID, "blas_threads must be in [1, 1024]");
     c->blas_threads = value;
   } else if (k == "refine_async") {
-    if (value && !c->rstream) {
+    vsig_ctx::RefineAsync& ra = c->ra;
+    if (value && !ra.stream) {
       // the highest stream priority: the refine's few blocks are dispatched
       // ahead of the next step's FIR blocks queued beside them (at the default
       // priority they waited for CU slots behind the FIR and spun for ~3 ms)
       int lo = 0, hi = 0;
       if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = hi = 0;
-      HIPCHK(c, hipStreamCreateWithPriority(&c->rstream, hipStreamNonBlocking, hi));
-      HIPCHK(c, hipEventCreateWithFlags(&c->ev_corr, hipEventDisableTiming));
-      HIPCHK(c, hipEventCreateWithFlags(&c->ev_ref, hipEventDisableTiming));
+      HIPCHK(c, hipStreamCreateWithPriority(&ra.stream, hipStreamNonBlocking, hi));
+      HIPCHK(c, hipEventCreateWithFlags(&ra.ev_corr, hipEventDisableTiming));
+      HIPCHK(c, hipEventCreateWithFlags(&ra.ev_ref, hipEventDisableTiming));
     }
     if (!value) join_refine(c);
     c->refine_async = value != 0;
@@ -686,7 +738,7 @@ int vsig_get_option(const vsig_ctx* c, const char* key, int* value) {
 
 void* vsig_refine_stream(vsig_ctx* c) {
   if (!c) return nullptr;
-  return (void*)(c->refine_async && c->rstream ? c->rstream : c->stream);
+  return (void*)(c->refine_async && c->ra.stream ? c->ra.stream : c->stream);
 }
 
 int vsig_refine_join(vsig_ctx* c) {
@@ -700,27 +752,21 @@ int vsig_refine_status(vsig_ctx* c, int32_t* status, int64_t* candidates) {
   *status = 2;
   *candidates = 0;
   join_refine(c);
-  if (!c->refine_ran || !c->rscratch) return VSIG_OK;
-  // refine.hip RefineKeys: count, lo_inv, hi_p1, status, done, fault
-  unsigned long long keys[6];
-  HIPCHK(c, hipMemcpyAsync(keys, c->rscratch, sizeof(keys), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *candidates = (int64_t)keys[0];
-  if (keys[5]) {
+  if (!c->refine_ran || !c->rscratch.data()) return VSIG_OK;
+  vsig::RefineKeys keys;
+  int rc = read_refine_keys(c, &keys);
+  if (rc) return rc;
+  *candidates = (int64_t)keys.count;
+  if (keys.fault) {
     // a watchdog fired in some refine since the last report: status 3 once,
     // then the fused launch's counters and the keys (fault word included) are
-    // cleared -- a fire can leave them inconsistent, and the next launch must
-    // start from zero -- and the record is not to be trusted until then
+    // cleared, and the record is not to be trusted until then
     *status = 3;
-    HIPCHK(c, hipMemsetAsync(c->rscratch, 0, kRefineKeysBytes, c->stream));
-    if (c->partials)
-      HIPCHK(c, hipMemsetAsync(c->partials + c->npartials + vsig::kFinalizeTmp, 0,
-                               vsig::kCounterRecs * sizeof(PeakPartial), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = clear_refine_fault(c))) return rc;
     c->refine_ran = false;
     return VSIG_OK;
   }
-  *status = keys[3] ? 1 : 0;
+  *status = keys.status ? 1 : 0;
   return VSIG_OK;
 }
 
@@ -759,8 +805,8 @@ int vsig_synchronize(vsig_ctx* c) {
 int vsig_clock_enable(vsig_ctx* c, int on) {
   if (!c) return VSIG_E_INVALID;
   if (on) {
-    if (!c->clkbuf) HIPCHK(c, hipMalloc(&c->clkbuf, 2 * kClockSlots * sizeof(unsigned long long)));
-    HIPCHK(c, hipMemsetAsync(c->clkbuf, 0, 2 * kClockSlots * sizeof(unsigned long long), c->stream));
+    if (!c->clkbuf.data()) HIPCHK(c, c->clkbuf.alloc(2 * kClockSlots * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->clkbuf.data(), 0, c->clkbuf.bytes(), c->stream));
   }
   c->clock = on != 0;
   return VSIG_OK;
@@ -771,10 +817,11 @@ int vsig_clock_read(vsig_ctx* c, const char* kernel, double* ghz, int64_t* ticks
   *ghz = 0.0;
   if (ticks) *ticks = 0;
   auto it = c->clkslot.find(kernel);
-  if (!c->clkbuf || it == c->clkslot.end()) return VSIG_OK;
+  if (!c->clkbuf.data() || it == c->clkslot.end()) return VSIG_OK;
   unsigned long long h[2] = {0, 0};
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(h, c->clkbuf + 2 * it->second, sizeof(h), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(h, c->clkbuf.as<unsigned long long>() + 2 * it->second, sizeof(h),
+                      hipMemcpyDeviceToHost));
   if (h[1]) *ghz = (double)h[0] / (double)h[1] * 0.1;      // s_memrealtime runs at 100 MHz
   if (ticks) *ticks = (int64_t)h[1];
   return VSIG_OK;
@@ -837,16 +884,16 @@ int vsig_psd_c64_dev(vsig_ctx* c, const void* x, int64_t n, int64_t stride, cons
     long long fb = (256LL << 20) / ((long long)nfft * 8);   // frames per 256 MB of scratch
     if (fb < 1) fb = 1;
     if (fb > nframes) fb = nframes;
-    if ((rc = ensure_buf(c, &c->bigtmp, &c->bigtmp_bytes, (size_t)(fb * nfft) * sizeof(float2)))) return rc;
+    if ((rc = c->bigtmp.reserve(c, (size_t)(fb * nfft) * sizeof(float2)))) return rc;
+    float2* tmp = c->bigtmp.as<float2>();
     Timed t(c, "psd");
     for (long long f0 = 0; f0 < nframes; f0 += fb) {
       const long long nb = nframes - f0 < fb ? nframes - f0 : fb;
       vsig::BigIn in{(const float2*)x + f0 * hop * stride, 0, hop * stride, stride, nperseg, nullptr,
                      win, 0, 1.0f};
-      HIPCHK(c, vsig::launch_bf_col(bp.N1, bp.N2, nb, in, (float2*)c->bigtmp, bp.tw1, bp.t2, bp.S,
-                                    bp.hiA, c->stream));
-      HIPCHK(c, vsig::launch_bf_row(2, bp.N1, bp.N2, nb, (float2*)c->bigtmp, nullptr, bp.tw2, scale,
-                                    sxx + f0 * nfft, shift, c->stream));
+      HIPCHK(c, vsig::launch_bf_col(bp.N1, bp.N2, nb, in, tmp, bp.tw1, bp.t2, bp.S, bp.hiA, c->stream));
+      HIPCHK(c, vsig::launch_bf_row(2, bp.N1, bp.N2, nb, tmp, nullptr, bp.tw2, scale, sxx + f0 * nfft,
+                                    shift, c->stream));
     }
     return VSIG_OK;
   }
@@ -868,14 +915,11 @@ int vsig_psd_c64(vsig_ctx* c, const void* x, int64_t n, const float* win, int32_
   if (n < nperseg || nperseg < 1 || hop < 1) return fail(c, VSIG_E_INVALID, "bad sizes");
   const size_t bx = (size_t)n * 8, bw = (size_t)nperseg * 4, bo = (size_t)nframes * nfft * 4;
   int rc;
-  if ((rc = ensure_stage(c, 0, bx)) || (rc = ensure_stage(c, 1, bw)) || (rc = ensure_stage(c, 2, bo)))
+  if ((rc = stage_in(c, 0, x, bx)) || (rc = stage_in(c, 1, win, bw)) || (rc = c->stage[2].reserve(c, bo)))
     return rc;
-  HIPCHK(c, hipMemcpyAsync(c->stage[0], x, bx, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->stage[1], win, bw, hipMemcpyHostToDevice, c->stream));
-  rc = vsig_psd_c64_dev(c, c->stage[0], n, 1, (const float*)c->stage[1], nperseg, hop, nfft, scale,
-                        shift, (float*)c->stage[2], nframes);
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(sxx, c->stage[2], bo, hipMemcpyDeviceToHost, c->stream));
+  rc = vsig_psd_c64_dev(c, c->stage[0].data(), n, 1, c->stage[1].as<float>(), nperseg, hop, nfft, scale,
+                        shift, c->stage[2].as<float>(), nframes);
+  if (rc || (rc = stage_out(c, sxx, c->stage[2], bo))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return VSIG_OK;
 }
@@ -886,16 +930,16 @@ int vsig_fir_create(vsig_ctx* c, const void* taps, int32_t ntaps, int32_t decim,
   *out = nullptr;
   if (ntaps < 1 || decim < 1) return fail(c, VSIG_E_INVALID, "ntaps and decim must be >= 1");
   if (ntaps > kFirPartTaps) {        // np.convolve has no length limit: parts
-    auto* f = new vsig_fir{c, ntaps, decim, 0, 0, nullptr};
+    std::unique_ptr<vsig_fir> f(new vsig_fir{c, ntaps, decim, 0, 0});
     for (int j = 0; j * kFirPartTaps < ntaps; ++j) {
       const int nt = ntaps - j * kFirPartTaps < kFirPartTaps ? ntaps - j * kFirPartTaps : kFirPartTaps;
       vsig_fir* p = nullptr;
       const int rc = vsig_fir_create(c, static_cast<const float2*>(taps) + (size_t)j * kFirPartTaps, nt, 1, &p);
-      if (rc) { vsig_fir_free(f); return rc; }
+      if (rc) return rc;
       f->parts.push_back(p);
     }
     f->M = f->parts[0]->M;
-    *out = f;
+    *out = f.release();
     return VSIG_OK;
   }
   const int M = os_size_fir(ntaps);
@@ -907,38 +951,24 @@ int vsig_fir_create(vsig_ctx* c, const void* taps, int32_t ntaps, int32_t decim,
   // pair instead of 16 for <= 4 % more segments (0.84 -> 0.80 ms at config 2,
   // profiles/r03_pl1_ab.txt)
   if (M == 1024 && decim == 1 && hop > 768 && hop < 800) hop = 768;
-  float2* hd = nullptr;
-  HIPCHK(c, hipMalloc(&hd, (size_t)ntaps * sizeof(float2)));
-  hipError_t e = hipMemcpyAsync(hd, taps, (size_t)ntaps * sizeof(float2), hipMemcpyHostToDevice, c->stream);
-  if (e != hipSuccess) { (void)hipFree(hd); return fail(c, VSIG_E_HIP, hipGetErrorString(e)); }
-  float2* Hs = nullptr;
-  int rc = make_spectrum(c, hd, ntaps, M, &Hs);
-  float2* G = nullptr;
+  DevBuf hd, Hs, G;      // hd: the taps on the device, dropped on return
+  HIPCHK(c, hd.alloc((size_t)ntaps * sizeof(float2)));
+  hipError_t e = hipMemcpyAsync(hd.data(), taps, (size_t)ntaps * sizeof(float2), hipMemcpyHostToDevice,
+                                c->stream);
+  if (e != hipSuccess) return fail(c, VSIG_E_HIP, hipGetErrorString(e));
+  int rc = make_spectrum(c, hd.as<float2>(), ntaps, M, &Hs);
   if (!rc && M == 1024 && decim == 4) {
-    hipError_t ge = hipMalloc(&G, 1024 * sizeof(float2));
-    if (ge == hipSuccess) ge = vsig::launch_fir_poly_gtable(Hs, G, c->stream);
+    hipError_t ge = G.alloc(1024 * sizeof(float2));
+    if (ge == hipSuccess) ge = vsig::launch_fir_poly_gtable(Hs.as<float2>(), G.as<float2>(), c->stream);
     if (ge != hipSuccess) rc = fail(c, VSIG_E_HIP, hipGetErrorString(ge));
   }
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(hd);
-  if (rc) {
-    (void)hipFree(Hs);
-    (void)hipFree(G);
-    return rc;
-  }
-  *out = new vsig_fir{c, ntaps, decim, M, hop, Hs, G};
+  (void)hipStreamSynchronize(c->stream);     // hd and the caller's taps are free to go
+  if (rc) return rc;
+  *out = new vsig_fir{c, ntaps, decim, M, hop, std::move(Hs), std::move(G)};
   return VSIG_OK;
 }
 
-void vsig_fir_free(vsig_fir* f) {
-  if (!f) return;
-  (void)hipStreamSynchronize(f->ctx->stream);
-  for (vsig_fir* p : f->parts) vsig_fir_free(p);
-  (void)hipFree(f->z);
-  (void)hipFree(f->Hs);
-  (void)hipFree(f->G);
-  delete f;
-}
+void vsig_fir_free(vsig_fir* f) { delete f; }
 
 static int fir_exec(vsig_fir* f, const void* x, int64_t nhist, int64_t n, void* y, int64_t ny,
                     const vsig::MixArgs* mix) {
@@ -952,12 +982,12 @@ static int fir_exec(vsig_fir* f, const void* x, int64_t nhist, int64_t n, void* 
   if (!f->parts.empty()) {
     if (mix) return fail(c, VSIG_E_UNSUPPORTED, "fused mixer needs ntaps <= 256 (mix first)");
     const long long nz = nhist + n;
-    if ((rc = ensure_buf(c, reinterpret_cast<void**>(&f->z), &f->zbytes, (size_t)nz * sizeof(float2))))
-      return rc;
+    if ((rc = f->z.reserve(c, (size_t)nz * sizeof(float2)))) return rc;
+    float2* z = f->z.as<float2>();
     for (size_t j = 0; j < f->parts.size(); ++j) {
-      if ((rc = fir_exec(f->parts[j], x, 0, nz, f->z, nz, nullptr))) return rc;
+      if ((rc = fir_exec(f->parts[j], x, 0, nz, z, nz, nullptr))) return rc;
       Timed t(c, "fir");
-      HIPCHK(c, vsig::launch_fir_part_accum(f->z, nz, nhist - (long long)j * kFirPartTaps, f->decim, ny,
+      HIPCHK(c, vsig::launch_fir_part_accum(z, nz, nhist - (long long)j * kFirPartTaps, f->decim, ny,
                                             j == 0, (float2*)y, c->stream));
     }
     return VSIG_OK;
@@ -973,17 +1003,17 @@ static int fir_exec(vsig_fir* f, const void* x, int64_t nhist, int64_t n, void* 
     if (((lo2 + 15) & ~15) + 768 <= f->M) lo2 = (lo2 + 15) & ~15;
     const long long hop = (long long)(f->M - lo2) / D * D;
     if (hop < D) return fail(c, VSIG_E_UNSUPPORTED, "decim too large for the block size");
-    if (f->G) {      // D = 4: polyphase form (fir_poly_kernel)
+    if (f->G.data()) {      // D = 4: polyphase form (fir_poly_kernel)
       if ((rc = get_twiddles(c, 256, &tw)) || (rc = get_twiddles(c, -256, &twd))) return rc;
       Timed t(c, "fir");
-      HIPCHK(c, vsig::launch_fir_poly((const float2*)x, nhist + n, nhist, f->G, lo2, hop, (float2*)y, tw,
-                                      twd, c->stream, mix));
+      HIPCHK(c, vsig::launch_fir_poly((const float2*)x, nhist + n, nhist, f->G.as<float2>(), lo2, hop,
+                                      (float2*)y, tw, twd, c->stream, mix));
       return VSIG_OK;
     }
     if ((rc = get_twiddles(c, -1024, &tw)) || (rc = get_twiddles(c, -1024 / f->decim, &twd))) return rc;
     Timed t(c, "fir");
-    HIPCHK(c, vsig::launch_fir_dec(D, (const float2*)x, nhist + n, nhist, f->Hs, lo2, hop, (float2*)y,
-                                   tw, twd, c->stream, mix));
+    HIPCHK(c, vsig::launch_fir_dec(D, (const float2*)x, nhist + n, nhist, f->Hs.as<float2>(), lo2, hop,
+                                   (float2*)y, tw, twd, c->stream, mix));
     return VSIG_OK;
   }
   if (mix && f->M != 1024)
@@ -991,8 +1021,8 @@ static int fir_exec(vsig_fir* f, const void* x, int64_t nhist, int64_t n, void* 
   rc = get_twiddles(c, f->M == 1024 ? -1024 : f->M, &tw);
   if (rc) return rc;
   Timed t(c, "fir");
-  HIPCHK(c, vsig::launch_fir_os(f->M, (const float2*)x, nhist + n, nhist, f->Hs, f->ntaps, f->hop,
-                                f->decim, (float2*)y, tw, c->stream, mix));
+  HIPCHK(c, vsig::launch_fir_os(f->M, (const float2*)x, nhist + n, nhist, f->Hs.as<float2>(), f->ntaps,
+                                f->hop, f->decim, (float2*)y, tw, c->stream, mix));
   return VSIG_OK;
 }
 
@@ -1035,17 +1065,13 @@ int vsig_fir_c64(vsig_ctx* c, const void* x, int64_t n, const float* taps, int32
   vsig_fir* f = nullptr;
   int rc = vsig_fir_create(c, tc.data(), ntaps, decim, &f);
   if (rc) return rc;
+  const std::unique_ptr<vsig_fir> owner(f);     // freed on every path below
   const size_t bx = (size_t)n * 8, by = (size_t)ny * 8;
-  if ((rc = ensure_stage(c, 0, bx)) || (rc = ensure_stage(c, 1, by))) { vsig_fir_free(f); return rc; }
-  hipError_t e = hipMemcpyAsync(c->stage[0], x, bx, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    rc = vsig_fir_exec_dev(f, c->stage[0], n, c->stage[1], ny);
-    if (!rc) e = hipMemcpyAsync(y, c->stage[1], by, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  vsig_fir_free(f);
-  if (rc) return rc;
-  if (e != hipSuccess) return fail(c, VSIG_E_HIP, hipGetErrorString(e));
+  if ((rc = stage_in(c, 0, x, bx)) || (rc = c->stage[1].reserve(c, by)) ||
+      (rc = vsig_fir_exec_dev(f, c->stage[0].data(), n, c->stage[1].data(), ny)) ||
+      (rc = stage_out(c, y, c->stage[1], by)))
+    return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return VSIG_OK;
 }
 
@@ -1055,29 +1081,18 @@ int vsig_fir_c64(vsig_ctx* c, const void* x, int64_t n, const float* taps, int32
 // chunk (sum of passes, see xcorr_run).
 static int xcorr_build(vsig_ctx* c, const float2* td, long long L, vsig_xcorr* x) {
   constexpr long long B = 8192;
-  x->ctx = c;
   x->L = L;
   x->M = os_size_xcorr(L) ? os_size_xcorr(L) : 16384;
   const long long Bc = x->M == 32768 ? 16384 : B;    // one pass up to 16384 at M = 32768
   for (long long p = 0; p * Bc < L || p == 0; ++p) {
     const long long Lp = L <= Bc ? L : ((L - p * Bc) < B ? (L - p * Bc) : B);
-    float2* P = nullptr;
+    DevBuf P;
     const int rc = make_spectrum(c, td + p * B, (int)Lp, x->M, &P);
     if (rc) return rc;
-    x->Ps.push_back(P);
+    x->Ps.push_back(std::move(P));
     if (L <= Bc) break;
   }
   return VSIG_OK;
-}
-
-static void xcorr_release(vsig_xcorr* x) {
-  (void)hipStreamSynchronize(x->ctx->stream);
-  for (float2* P : x->Ps) (void)hipFree(P);
-  x->Ps.clear();
-  if (x->tmpl) (void)hipFree(x->tmpl);
-  if (x->cbuf) (void)hipFree(x->cbuf);
-  x->tmpl = nullptr;
-  x->cbuf = nullptr;
 }
 
 // The correlation c[o] = sum_k s[o - off + k] conj(p[k]) of the handle's
@@ -1091,7 +1106,7 @@ static int xcorr_run(vsig_xcorr* x, const float2* s, long long n, long long off,
                      int store_mode, float2* cout, vsig_peak_t* peak_dev,
                      const RefineOperands* op, void* out128, bool async = false) {
   vsig_ctx* c = x->ctx;
-  PeakPartial* rec = peak_dev ? reinterpret_cast<PeakPartial*>(peak_dev) : c->result;
+  PeakPartial* rec = peak_record(c, peak_dev);
   if (x->Ps.size() == 1 && x->L <= (x->M == 32768 ? 16384 : 8192)) {
     // outputs per block: M - L + 1, rounded down to even at M = 16384 (every
     // segment start then has one parity: the correlator's 16-byte loads)
@@ -1110,9 +1125,8 @@ static int xcorr_run(vsig_xcorr* x, const float2* s, long long n, long long off,
     const bool fused = op && c->refine && !(store_mode & 8);
     unsigned* lk = nullptr;
     if (fused && Q <= 64 && vsig::xcorr_lane_keys(x->M) == Q) {
-      if ((rc = ensure_buf(c, &c->lkeys, &c->lkeys_bytes, (size_t)nparts * 64 * sizeof(unsigned))))
-        return rc;
-      lk = static_cast<unsigned*>(c->lkeys);
+      if ((rc = c->lkeys.reserve(c, (size_t)nparts * 64 * sizeof(unsigned)))) return rc;
+      lk = c->lkeys.as<unsigned>();
     }
     const float2* tw;
     const float2* wt = nullptr;
@@ -1120,8 +1134,8 @@ static int xcorr_run(vsig_xcorr* x, const float2* s, long long n, long long off,
     if (x->M >= 16384 && (rc = get_half_tw(c, x->M, x->M == 16384 ? 512 : 1024, &wt))) return rc;
     {
       Timed t(c, "xcorr");
-      HIPCHK(c, vsig::launch_xcorr_os(x->M, s, n, x->Ps[0], off, nout, hop, cout, store_mode,
-                                      c->partials, tw, wt, c->stream, lk));
+      HIPCHK(c, vsig::launch_xcorr_os(x->M, s, n, x->Ps[0].as<float2>(), off, nout, hop, cout, store_mode,
+                                      c->parts(), tw, wt, c->stream, lk));
     }
     if (!fused) {
       if ((rc = finalize_peak(c, nparts, 1, peak_dev))) return rc;
@@ -1136,8 +1150,8 @@ static int xcorr_run(vsig_xcorr* x, const float2* s, long long n, long long off,
   float2* cbuf = cout;
   int rc;
   if (!cbuf) {
-    if ((rc = ensure_buf(c, &x->cbuf, &x->cbuf_bytes, (size_t)nout * sizeof(float2)))) return rc;
-    cbuf = static_cast<float2*>(x->cbuf);
+    if ((rc = x->cbuf.reserve(c, (size_t)nout * sizeof(float2)))) return rc;
+    cbuf = x->cbuf.as<float2>();
   }
   const float2 *tw, *wt;
   int waves, Q, stride, plan, wstep, rsub;
@@ -1149,7 +1163,7 @@ static int xcorr_run(vsig_xcorr* x, const float2* s, long long n, long long off,
     for (size_t p = 0; p < x->Ps.size(); ++p) {
       const long long Lp = (x->L - (long long)p * B) < B ? (x->L - (long long)p * B) : B;
       const int mode = (store_mode & 4 ? 2 | 4 : 1) | (p ? 8 : 0);
-      HIPCHK(c, vsig::launch_xcorr_os(M, s, n, x->Ps[p], off - (long long)p * B, nout,
+      HIPCHK(c, vsig::launch_xcorr_os(M, s, n, x->Ps[p].as<float2>(), off - (long long)p * B, nout,
                                       (long long)M - Lp + 1, cbuf, mode, nullptr, tw, wt,
                                       c->stream));
     }
@@ -1164,32 +1178,20 @@ int vsig_xcorr_create(vsig_ctx* c, const void* tmpl, int64_t L, vsig_xcorr** out
   if (!c || !tmpl || !out) return fail(c, VSIG_E_INVALID, "null pointer");
   *out = nullptr;
   if (L < 1) return fail(c, VSIG_E_INVALID, "template length must be >= 1");
-  vsig_xcorr* x = new vsig_xcorr();
-  x->ctx = c;
-  hipError_t e = hipMalloc(&x->tmpl, (size_t)L * sizeof(float2));
+  std::unique_ptr<vsig_xcorr> x(new vsig_xcorr(c));
+  hipError_t e = x->tmpl.alloc((size_t)L * sizeof(float2));
   if (e == hipSuccess)
-    e = hipMemcpyAsync(x->tmpl, tmpl, (size_t)L * sizeof(float2), hipMemcpyHostToDevice, c->stream);
-  if (e != hipSuccess) {
-    xcorr_release(x);
-    delete x;
+    e = hipMemcpyAsync(x->tmpl.data(), tmpl, (size_t)L * sizeof(float2), hipMemcpyHostToDevice, c->stream);
+  if (e != hipSuccess)
     return fail(c, e == hipErrorOutOfMemory ? VSIG_E_NOMEM : VSIG_E_HIP, hipGetErrorString(e));
-  }
-  const int rc = xcorr_build(c, x->tmpl, L, x);
-  (void)hipStreamSynchronize(c->stream);
-  if (rc) {
-    xcorr_release(x);
-    delete x;
-    return rc;
-  }
-  *out = x;
+  const int rc = xcorr_build(c, x->tmpl.as<float2>(), L, x.get());
+  (void)hipStreamSynchronize(c->stream);     // the caller's template is free to go
+  if (rc) return rc;
+  *out = x.release();
   return VSIG_OK;
 }
 
-void vsig_xcorr_free(vsig_xcorr* x) {
-  if (!x) return;
-  xcorr_release(x);
-  delete x;
-}
+void vsig_xcorr_free(vsig_xcorr* x) { delete x; }
 
 int vsig_xcorr_exec_dev(vsig_xcorr* x, const void* s, int64_t n, int32_t mode, void* cout,
                         vsig_peak_t* peak_dev) {
@@ -1202,7 +1204,7 @@ int vsig_xcorr_exec_dev(vsig_xcorr* x, const void* s, int64_t n, int32_t mode, v
   else return fail(c, VSIG_E_INVALID, "streaming correlation supports VALID and FULL");
   if (nout < 1) return fail(c, VSIG_E_INVALID, "stream shorter than the template");
   // np.correlate(s, p): output o is full index (L - 1 - off) + o
-  const RefineOperands op{s, n, x->tmpl, x->L, 0, (x->L - 1) - off};
+  const RefineOperands op{s, n, x->tmpl.data(), x->L, 0, (x->L - 1) - off};
   return xcorr_run(x, (const float2*)s, n, off, nout, cout ? 1 : 0, (float2*)cout, peak_dev, &op,
                    nullptr, true);
 }
@@ -1215,27 +1217,23 @@ static int correlate_impl(vsig_ctx* c, int in128, const void* a, long long na, c
   if (!c || !a || !v) return fail(c, VSIG_E_INVALID, "null pointer");
   if (na < 1 || nv < 1) return fail(c, VSIG_E_INVALID, "empty input");  // numeric.py:865-868
   const long long nmin = na < nv ? na : nv, nmax = na < nv ? nv : na;
-  long long F, nout;  // start index into the 'full' correlation, output length
-  if (mode == VSIG_MODE_FULL) { F = 0; nout = na + nv - 1; }
-  else if (mode == VSIG_MODE_VALID) { F = nmin - 1; nout = nmax - nmin + 1; }
-  else if (mode == VSIG_MODE_SAME) { F = na >= nv ? nmin - 1 - nmin / 2 : nmin / 2; nout = nmax; }
-  else return fail(c, VSIG_E_INVALID, "mode must be VALID, FULL or SAME");
+  long long F, nout;
+  if (!corr_span(mode, na, nv, &F, &nout)) return fail(c, VSIG_E_INVALID, "mode must be VALID, FULL or SAME");
   int rc;
   // complex64 operands of the FFT pass (complex128 callers: converted copies)
   const float2 *a64 = (const float2*)a, *v64 = (const float2*)v;
   if (in128) {
-    if ((rc = ensure_buf(c, &c->conv[0], &c->conv_bytes[0], (size_t)na * 8)) ||
-        (rc = ensure_buf(c, &c->conv[1], &c->conv_bytes[1], (size_t)nv * 8)))
+    if ((rc = c->conv[0].reserve(c, (size_t)na * 8)) || (rc = c->conv[1].reserve(c, (size_t)nv * 8)))
       return rc;
-    HIPCHK(c, vsig::launch_convert_c(0, a, na, c->conv[0], c->stream));
-    HIPCHK(c, vsig::launch_convert_c(0, v, nv, c->conv[1], c->stream));
-    a64 = (const float2*)c->conv[0];
-    v64 = (const float2*)c->conv[1];
+    HIPCHK(c, vsig::launch_convert_c(0, a, na, c->conv[0].data(), c->stream));
+    HIPCHK(c, vsig::launch_convert_c(0, v, nv, c->conv[1].data(), c->stream));
+    a64 = c->conv[0].as<float2>();
+    v64 = c->conv[1].as<float2>();
   }
   float2* c64 = (float2*)cout;
   if (out128 && cout) {
-    if ((rc = ensure_buf(c, &c->conv[2], &c->conv_bytes[2], (size_t)nout * 8))) return rc;
-    c64 = (float2*)c->conv[2];
+    if ((rc = c->conv[2].reserve(c, (size_t)nout * 8))) return rc;
+    c64 = c->conv[2].as<float2>();
   }
   const bool swap = nv > na;  // template must be the shorter operand
   const float2* tmpl = swap ? a64 : v64;
@@ -1244,23 +1242,17 @@ static int correlate_impl(vsig_ctx* c, int in128, const void* a, long long na, c
   // Not swapped: kernel offset off = (L-1) - F.  Swapped: compute the
   // correlation of v by a and store conj() reversed, off' = F + nout - nv.
   const long long off = swap ? F + nout - nv : (nmin - 1) - F;
-  vsig_xcorr x;
-  x.ctx = c;
-  rc = xcorr_build(c, tmpl, nmin, &x);
-  if (!rc) {
-    const RefineOperands op{a, na, v, nv, in128, F};
-    const int store = (cout ? (swap ? 2 : 1) : 0) | (swap ? 4 : 0);
-    rc = xcorr_run(&x, strm, nmax, off, nout, store, c64, peak_dev, &op, out128 ? cout : nullptr);
-  }
-  xcorr_release(&x);     // synchronises before freeing the template spectra
-  return rc;
+  vsig_xcorr x(c);       // its destructor synchronises before the template spectra are freed
+  if ((rc = xcorr_build(c, tmpl, nmin, &x))) return rc;
+  const RefineOperands op{a, na, v, nv, in128, F};
+  const int store = (cout ? (swap ? 2 : 1) : 0) | (swap ? 4 : 0);
+  return xcorr_run(&x, strm, nmax, off, nout, store, c64, peak_dev, &op, out128 ? cout : nullptr);
 }
 
 int vsig_correlate_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t na, const void* v,
                        int64_t nv, int32_t mode, int32_t out_dtype, void* cout,
                        vsig_peak_t* peak_dev) {
-  if ((dtype != VSIG_DTYPE_C64 && dtype != VSIG_DTYPE_C128) ||
-      (out_dtype != VSIG_DTYPE_C64 && out_dtype != VSIG_DTYPE_C128))
+  if (!is_complex_dtype(dtype) || !is_complex_dtype(out_dtype))
     return fail(c, VSIG_E_INVALID, "dtype must be VSIG_DTYPE_C64 or VSIG_DTYPE_C128");
   return correlate_impl(c, dtype == VSIG_DTYPE_C128, a, na, v, nv, mode,
                         out_dtype == VSIG_DTYPE_C128, cout, peak_dev);
@@ -1275,24 +1267,20 @@ int vsig_correlate(vsig_ctx* c, int32_t dtype, const void* a, int64_t na, const 
                    int64_t nv, int32_t mode, int32_t out_dtype, void* cout, vsig_peak_t* peak) {
   if (!c || !a || !v) return fail(c, VSIG_E_INVALID, "null pointer");
   if (na < 1 || nv < 1) return fail(c, VSIG_E_INVALID, "empty input");
-  if ((dtype != VSIG_DTYPE_C64 && dtype != VSIG_DTYPE_C128) ||
-      (out_dtype != VSIG_DTYPE_C64 && out_dtype != VSIG_DTYPE_C128))
+  if (!is_complex_dtype(dtype) || !is_complex_dtype(out_dtype))
     return fail(c, VSIG_E_INVALID, "dtype must be VSIG_DTYPE_C64 or VSIG_DTYPE_C128");
   const size_t es = dtype == VSIG_DTYPE_C128 ? 16 : 8, eo = out_dtype == VSIG_DTYPE_C128 ? 16 : 8;
-  const long long nmin = na < nv ? na : nv, nmax = na < nv ? nv : na;
-  const long long nout = mode == VSIG_MODE_FULL ? na + nv - 1
-                       : mode == VSIG_MODE_VALID ? nmax - nmin + 1 : nmax;
+  long long F, nout;
+  if (!corr_span(mode, na, nv, &F, &nout)) return fail(c, VSIG_E_INVALID, "mode must be VALID, FULL or SAME");
   int rc;
-  if ((rc = ensure_stage(c, 0, (size_t)na * es)) || (rc = ensure_stage(c, 1, (size_t)nv * es)) ||
-      (cout && (rc = ensure_stage(c, 2, (size_t)nout * eo))))
+  if ((rc = stage_in(c, 0, a, (size_t)na * es)) || (rc = stage_in(c, 1, v, (size_t)nv * es)) ||
+      (cout && (rc = c->stage[2].reserve(c, (size_t)nout * eo))))
     return rc;
-  HIPCHK(c, hipMemcpyAsync(c->stage[0], a, (size_t)na * es, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->stage[1], v, (size_t)nv * es, hipMemcpyHostToDevice, c->stream));
-  rc = vsig_correlate_dev(c, dtype, c->stage[0], na, c->stage[1], nv, mode, out_dtype,
-                          cout ? c->stage[2] : nullptr, nullptr);
-  if (rc) return rc;
-  if (cout) HIPCHK(c, hipMemcpyAsync(cout, c->stage[2], (size_t)nout * eo, hipMemcpyDeviceToHost, c->stream));
-  if (peak) HIPCHK(c, hipMemcpyAsync(peak, c->result, sizeof(vsig_peak_t), hipMemcpyDeviceToHost, c->stream));
+  rc = vsig_correlate_dev(c, dtype, c->stage[0].data(), na, c->stage[1].data(), nv, mode, out_dtype,
+                          cout ? c->stage[2].data() : nullptr, nullptr);
+  if (rc || (cout && (rc = stage_out(c, cout, c->stage[2], (size_t)nout * eo))) ||
+      (peak && (rc = stage_out(c, peak, c->result, sizeof(vsig_peak_t)))))
+    return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return VSIG_OK;
 }
@@ -1307,8 +1295,7 @@ int vsig_dft_dev(vsig_ctx* c, int32_t dtype, const void* x, int64_t n, int64_t b
                  int32_t out_dtype, void* y) {
   if (!c || !x || !y) return fail(c, VSIG_E_INVALID, "null pointer");
   if (n < 1 || batch < 1) return fail(c, VSIG_E_INVALID, "need n >= 1 and batch >= 1");
-  if ((dtype != VSIG_DTYPE_C64 && dtype != VSIG_DTYPE_C128) ||
-      (out_dtype != VSIG_DTYPE_C64 && out_dtype != VSIG_DTYPE_C128))
+  if (!is_complex_dtype(dtype) || !is_complex_dtype(out_dtype))
     return fail(c, VSIG_E_INVALID, "dtype must be VSIG_DTYPE_C64 or VSIG_DTYPE_C128");
   vsig::BigIn in{x, dtype == VSIG_DTYPE_C128 ? 1 : 0, n, 1, n, nullptr, nullptr, 0, 1.0f};
   vsig::BigOut out{y, out_dtype == VSIG_DTYPE_C128 ? 1 : 0, n, n, nullptr, 0,
@@ -1321,14 +1308,13 @@ int vsig_resample_dev(vsig_ctx* c, int32_t dtype, const void* x, int64_t n, int6
                       int32_t real_input, void* y) {
   if (!c || !x || !y) return fail(c, VSIG_E_INVALID, "null pointer");
   if (n < 1 || num < 1) return fail(c, VSIG_E_INVALID, "need n >= 1 and num >= 1");
-  if (dtype != VSIG_DTYPE_C64 && dtype != VSIG_DTYPE_C128)
+  if (!is_complex_dtype(dtype))
     return fail(c, VSIG_E_INVALID, "dtype must be VSIG_DTYPE_C64 or VSIG_DTYPE_C128");
   int rc;
-  if ((rc = ensure_buf(c, &c->spec[0], &c->spec_bytes[0], (size_t)n * 8)) ||
-      (rc = ensure_buf(c, &c->spec[1], &c->spec_bytes[1], (size_t)num * 8)))
+  if ((rc = c->spec[0].reserve(c, (size_t)n * 8)) || (rc = c->spec[1].reserve(c, (size_t)num * 8)))
     return rc;
-  float2* X = (float2*)c->spec[0];
-  float2* Y = (float2*)c->spec[1];
+  float2* X = c->spec[0].as<float2>();
+  float2* Y = c->spec[1].as<float2>();
   Timed t(c, "resample");
   vsig::BigIn in{x, dtype == VSIG_DTYPE_C128 ? 1 : 0, n, 1, n, nullptr, nullptr, 0, 1.0f};
   vsig::BigOut ox{X, 0, n, n, nullptr, 0, 1.0f};
@@ -1348,7 +1334,7 @@ int vsig_filter_channel_dev(vsig_ctx* c, int32_t dtype, const void* x, int64_t n
   if (n > 1 && (n & 1))
     return fail(c, VSIG_E_INVALID, "odd length: the conjugate mirror's halves differ (numpy "
                                    "raises on the shape mismatch)");
-  if (dtype != VSIG_DTYPE_C64 && dtype != VSIG_DTYPE_C128)
+  if (!is_complex_dtype(dtype))
     return fail(c, VSIG_E_INVALID, "dtype must be VSIG_DTYPE_C64 or VSIG_DTYPE_C128");
   const double center = 5230e6;                  // split_channels.py:7 CENTER_FREQ
   const double lo = center_freq - bandwidth / 2, hi = center_freq + bandwidth / 2;
@@ -1373,19 +1359,18 @@ int vsig_filter_channel_dev(vsig_ctx* c, int32_t dtype, const void* x, int64_t n
   const long long nk = kb >= ka ? kb - ka + 1 : 0;
   int rc;
   if (nk * n <= (1LL << 32)) {                   // direct double-precision path
-    if ((rc = ensure_buf(c, &c->spec[0], &c->spec_bytes[0], (size_t)(nk > 0 ? nk : 1) * 256 * 16)) ||
-        (rc = ensure_buf(c, &c->spec[1], &c->spec_bytes[1], (size_t)(nk > 0 ? nk : 1) * 16)))
+    if ((rc = c->spec[0].reserve(c, (size_t)(nk > 0 ? nk : 1) * 256 * 16)) ||
+        (rc = c->spec[1].reserve(c, (size_t)(nk > 0 ? nk : 1) * 16)))
       return rc;
     Timed t(c, "channel");
-    HIPCHK(c, vsig::launch_channel_direct(dtype == VSIG_DTYPE_C128, x, n, ka, kb, (double2*)c->spec[0],
-                                          (double2*)c->spec[1], y, c->stream));
+    HIPCHK(c, vsig::launch_channel_direct(dtype == VSIG_DTYPE_C128, x, n, ka, kb, c->spec[0].as<double2>(),
+                                          c->spec[1].as<double2>(), y, c->stream));
     return VSIG_OK;
   }
-  if ((rc = ensure_buf(c, &c->spec[0], &c->spec_bytes[0], (size_t)n * 8)) ||
-      (rc = ensure_buf(c, &c->spec[1], &c->spec_bytes[1], (size_t)n * 8)))
+  if ((rc = c->spec[0].reserve(c, (size_t)n * 8)) || (rc = c->spec[1].reserve(c, (size_t)n * 8)))
     return rc;
-  float2* X = (float2*)c->spec[0];
-  float2* F = (float2*)c->spec[1];
+  float2* X = c->spec[0].as<float2>();
+  float2* F = c->spec[1].as<float2>();
   Timed t(c, "channel");
   vsig::BigIn in{x, dtype == VSIG_DTYPE_C128 ? 1 : 0, n, 1, n, nullptr, nullptr, 0, 1.0f};
   vsig::BigOut ox{X, 0, n, n, nullptr, 0, 1.0f};
@@ -1408,7 +1393,7 @@ int vsig_peak_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, vsig_pea
   if (rc) return rc;
   {
     Timed t(c, "peak");
-    HIPCHK(c, vsig::launch_peak_reduce(dtype, a, n, c->partials, (int)nparts, c->stream));
+    HIPCHK(c, vsig::launch_peak_reduce(dtype, a, n, c->parts(), (int)nparts, c->stream));
   }
   return finalize_peak(c, nparts, 0, peak_dev);
 }
@@ -1417,12 +1402,10 @@ int vsig_peak(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, vsig_peak_t*
   if (!c || !a || !peak) return fail(c, VSIG_E_INVALID, "null pointer");
   if (n < 1) return fail(c, VSIG_E_INVALID, "empty input");
   const size_t es = dtype == VSIG_DTYPE_C128 ? 16 : (dtype == VSIG_DTYPE_F32 ? 4 : 8);
-  int rc = ensure_stage(c, 0, (size_t)n * es);
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->stage[0], a, (size_t)n * es, hipMemcpyHostToDevice, c->stream));
-  rc = vsig_peak_dev(c, dtype, c->stage[0], n, nullptr);
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(peak, c->result, sizeof(vsig_peak_t), hipMemcpyDeviceToHost, c->stream));
+  int rc;
+  if ((rc = stage_in(c, 0, a, (size_t)n * es)) || (rc = vsig_peak_dev(c, dtype, c->stage[0].data(), n, nullptr)) ||
+      (rc = stage_out(c, peak, c->result, sizeof(vsig_peak_t))))
+    return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return VSIG_OK;
 }
@@ -1434,10 +1417,10 @@ int vsig_abs_stats_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, dou
   if (n < 1) return fail(c, VSIG_E_INVALID, "empty input");
   if (dtype != VSIG_DTYPE_C128 && dtype != VSIG_DTYPE_F64)
     return fail(c, VSIG_E_UNSUPPORTED, "abs stats: dtype must be VSIG_DTYPE_C128 or VSIG_DTYPE_F64");
-  int rc = ensure_buf(c, &c->sscratch, &c->sscratch_bytes, vsig::np_stats_scratch_bytes(n));
+  int rc = c->sscratch.reserve(c, vsig::np_stats_scratch_bytes(n));
   if (rc) return rc;
   Timed t(c, "stats");
-  HIPCHK(c, vsig::launch_np_stats(dtype, a, n, stats_dev, c->sscratch, c->stream));
+  HIPCHK(c, vsig::launch_np_stats(dtype, a, n, stats_dev, c->sscratch.data(), c->stream));
   return VSIG_OK;
 }
 
@@ -1447,29 +1430,24 @@ int vsig_correlate_stats_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t 
                              int64_t nv, int32_t mode, double* stats_dev) {
   if (!c || !a || !v || !stats_dev) return fail(c, VSIG_E_INVALID, "null pointer");
   if (na < 1 || nv < 1) return fail(c, VSIG_E_INVALID, "empty input");
-  if (dtype != VSIG_DTYPE_C64 && dtype != VSIG_DTYPE_C128)
+  if (!is_complex_dtype(dtype))
     return fail(c, VSIG_E_INVALID, "dtype must be VSIG_DTYPE_C64 or VSIG_DTYPE_C128");
-  const long long nmin = na < nv ? na : nv, nmax = na < nv ? nv : na;
   long long F, nout;
-  if (mode == VSIG_MODE_FULL) { F = 0; nout = na + nv - 1; }
-  else if (mode == VSIG_MODE_VALID) { F = nmin - 1; nout = nmax - nmin + 1; }
-  else if (mode == VSIG_MODE_SAME) { F = na >= nv ? nmin - 1 - nmin / 2 : nmin / 2; nout = nmax; }
-  else return fail(c, VSIG_E_INVALID, "mode must be VALID, FULL or SAME");
+  if (!corr_span(mode, na, nv, &F, &nout)) return fail(c, VSIG_E_INVALID, "mode must be VALID, FULL or SAME");
   const size_t vb = ((size_t)nout * 8 + 255) & ~(size_t)255;
   const size_t kb = (vsig::refine_values_scratch_bytes() + 255) & ~(size_t)255;
-  int rc = ensure_buf(c, &c->vscratch, &c->vscratch_bytes, vb + kb);
-  if (rc) return rc;
-  if ((rc = ensure_buf(c, &c->sscratch, &c->sscratch_bytes, vsig::np_stats_scratch_bytes(nout))))
+  int rc;
+  if ((rc = c->vscratch.reserve(c, vb + kb)) || (rc = c->sscratch.reserve(c, vsig::np_stats_scratch_bytes(nout))))
     return rc;
-  double* vals = static_cast<double*>(c->vscratch);
+  double* vals = c->vscratch.as<double>();
   vsig::RefineArgs r{};
   r.a = a; r.na = na; r.v = v; r.nv = nv; r.c128 = dtype == VSIG_DTYPE_C128;
   r.nout = nout; r.F = F; r.waves = 1; r.Q = 1; r.rsub = 1;
   r.blas_threads = c->blas_threads;
-  r.scratch = static_cast<char*>(c->vscratch) + vb;
+  r.scratch = c->vscratch.as<char>() + vb;
   Timed t(c, "stats");
   HIPCHK(c, vsig::launch_refine_values(r, 0, nout - 1, vals, c->stream));
-  HIPCHK(c, vsig::launch_np_stats(VSIG_DTYPE_F64, vals, nout, stats_dev, c->sscratch, c->stream));
+  HIPCHK(c, vsig::launch_np_stats(VSIG_DTYPE_F64, vals, nout, stats_dev, c->sscratch.data(), c->stream));
   return VSIG_OK;
 }
 
@@ -1602,9 +1580,9 @@ int vsig_select_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, const 
   unsigned long long pf[4] = {0, 0, 0, 0}, mk[4] = {0, 0, 0, 0};
   long long k[4];
   for (int q = 0; q < nranks; ++q) k[q] = ranks[q];
-  int rc = ensure_stage(c, 2, 4096 * 8 + 64);
+  int rc = c->stage[2].reserve(c, 4096 * 8 + 64);
   if (rc) return rc;
-  unsigned long long* dhist = (unsigned long long*)c->stage[2];
+  unsigned long long* dhist = c->stage[2].as<unsigned long long>();
   unsigned long long* dpf = dhist + 4 * 256;
   unsigned long long* dmk = dpf + 4;
   std::vector<unsigned long long> h(4 * 256);
@@ -1652,11 +1630,11 @@ int vsig_threshold_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, dou
   if (n < 1) return fail(c, VSIG_E_INVALID, "empty input");
   long long nparts = (n + 255) / 256;
   if (nparts > 2048) nparts = 2048;
-  int rc = ensure_stage(c, 2, (size_t)nparts * sizeof(vsig::ThreshPartialH));
+  int rc = c->stage[2].reserve(c, (size_t)nparts * sizeof(vsig::ThreshPartialH));
   if (rc) return rc;
-  HIPCHK(c, vsig::launch_thresh_reduce(dtype, a, n, thr, c->stage[2], (int)nparts, c->stream));
+  HIPCHK(c, vsig::launch_thresh_reduce(dtype, a, n, thr, c->stage[2].data(), (int)nparts, c->stream));
   std::vector<vsig::ThreshPartialH> h(nparts);
-  HIPCHK(c, hipMemcpyAsync(h.data(), c->stage[2], nparts * sizeof(vsig::ThreshPartialH),
+  HIPCHK(c, hipMemcpyAsync(h.data(), c->stage[2].data(), nparts * sizeof(vsig::ThreshPartialH),
                            hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   long long cnt = 0, f = n, l = -1;
@@ -1681,9 +1659,9 @@ int vsig_boxcar_energy_dev(vsig_ctx* c, int32_t dtype, const void* x, int64_t n,
   if (n < 1 || w < 1) return fail(c, VSIG_E_INVALID, "need n >= 1, w >= 1");
   const long long nt = vsig::energy_scan_tiles(n);
   int rc;
-  if ((rc = ensure_stage(c, 1, (size_t)nt * 8)) || (rc = ensure_stage(c, 2, (size_t)n * 8))) return rc;
-  double* P = (double*)c->stage[2];
-  HIPCHK(c, vsig::launch_energy_prefix(dtype, x, n, (double*)c->stage[1], P, c->stream));
+  if ((rc = c->stage[1].reserve(c, (size_t)nt * 8)) || (rc = c->stage[2].reserve(c, (size_t)n * 8))) return rc;
+  double* P = c->stage[2].as<double>();
+  HIPCHK(c, vsig::launch_energy_prefix(dtype, x, n, c->stage[1].as<double>(), P, c->stream));
   HIPCHK(c, vsig::launch_boxcar_same(P, n, w, sm, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));   // stage buffers are reused by the next call
   return VSIG_OK;

@@ -206,6 +206,22 @@ struct RefineArgs {
   void* out128;                     // optional complex128 c to patch (final space)
   unsigned long long wd_ticks;      // fused launch's watchdog, 100 MHz ticks (0: 2 s)
 };
+// Header of the refine scratch (zeroed before select: by the fused finalize,
+// or a memset); the C-ABI layer reads count / status / fault back.
+struct RefineKeys {
+  unsigned long long count;    // candidate items appended by select
+  unsigned long long lo_inv;   // ~(lowest final output an item covers)  (atomic max)
+  unsigned long long hi_p1;    // highest final output an item covers + 1 (atomic max)
+  unsigned long long status;   // 1: more candidate outputs than the opt-in cap
+  unsigned long long done;     // numpy-pass blocks finished (the last one reduces)
+  unsigned long long fault;    // sticky: a refine_fused watchdog fired.  Nothing on
+                               // the device clears it (the finalize resets status,
+                               // not this); vsig_refine_status reports status 3 and
+                               // clears it with the launch's counters.
+  unsigned long long pad[2];
+};
+constexpr size_t kRefineKeysBytes = 64;
+static_assert(sizeof(RefineKeys) == kRefineKeysBytes, "the items follow the keys at +64 B");
 size_t refine_scratch_bytes(const RefineArgs& r);
 hipError_t launch_refine(const RefineArgs& r, hipStream_t st);
 // numpy's |c| of every output o in [lo, hi] into vals[o - lo] (operands and
