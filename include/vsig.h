@@ -361,6 +361,52 @@ int vsig_db_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, double f
 int vsig_abs_c64_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, void* out);
 int vsig_abs_c128_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, void* out);
 
+/* ---- peak list: every packet instance in a stored correlation (or the peaks
+ * of any array of dtype VSIG_DTYPE_*), where the entry points above stop at
+ * the one global argmax.  With m[i] = |a[i]| as vsig_peak_dev forms it
+ * (numpy's abs in the array's precision, widened to double), index i is an
+ * instance iff m[i] >= thr and i is the FIRST maximum of m over
+ * [max(0, i - min_distance), min(n - 1, i + min_distance)]; in numpy
+ * lo + np.argmax(m[lo:hi+1]) == i.  So two instances are more than
+ * min_distance apart, min_distance = 0 is plain threshold compaction, a flat
+ * array has the one instance 0, and a peak with a higher neighbour within
+ * min_distance is dropped even if that neighbour is dropped too (a maximum
+ * filter, not a greedy selection).  thr is absolute, or with relative != 0 a
+ * ratio: thr_used = thr * max(m), one double multiply on the device.
+ * out: the instances in ascending index order, at most cap records (the cap
+ *   lowest-index ones when there are more); may be NULL when cap == 0 (count
+ *   only).  Records past min(count, cap) are not written.
+ * info: always written; count is the exact number of instances whatever cap.
+ * The same input gives the same bytes on every run.  Cost: one pass over the
+ * array plus O(n log min_distance) compares in the worst case (every element
+ * above thr), nothing proportional to n * min_distance.
+ * n < 1, n > 2^40, cap < 0, min_distance < 0, a NULL a / info, a NULL out with
+ * cap > 0, an unknown dtype or a NaN thr: VSIG_E_INVALID before any work is
+ * enqueued.  Arrays that hold NaN are outside the contract: a NaN element is
+ * never an instance and never suppresses one, and all writes stay inside
+ * out[0..cap) and info.
+ * vsig_peaks_dev enqueues on the context stream, allocates nothing once its
+ * scratch is warm for n and never synchronises (capturable).  vsig_peaks takes
+ * host pointers (a, out, info) and returns when they are filled.
+ * vsig_peaks_tile: the kernels' tile length (elements); min_distance below it
+ * and from it upward take different paths. */
+typedef struct vsig_instance_t {
+  int64_t index;
+  double value;      /* |a[index]| */
+} vsig_instance_t;
+typedef struct vsig_peaks_info_t {
+  int64_t count;     /* instances in the array */
+  int64_t argmax;    /* index of the first max of |a| */
+  double max;        /* max |a| */
+  double thr_used;   /* the threshold applied */
+} vsig_peaks_info_t;
+int vsig_peaks_tile(void);
+int vsig_peaks_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, double thr,
+                   int32_t relative, int64_t min_distance, vsig_instance_t* out_dev, int64_t cap,
+                   vsig_peaks_info_t* info_dev);
+int vsig_peaks(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, double thr, int32_t relative,
+               int64_t min_distance, vsig_instance_t* out, int64_t cap, vsig_peaks_info_t* info);
+
 /* ---- time-chunk shard of the streaming chain (chain.hip; the C form of
  * vector_amd/shard.py StreamChain; reference precedent: the
  * overlapped chunking of heavy_packet_optimizer.py:114-152).  Rank r of world

@@ -66,6 +66,17 @@ class PacketPlace(C.Structure):
     """vsig_packet_place (include/vsig.h)."""
     _fields_ = [("y", P), ("len", I64), ("start", I64), ("period", I64), ("count", I64)]
 
+
+class Instance(C.Structure):
+    """vsig_instance_t (include/vsig.h)."""
+    _fields_ = [("index", I64), ("value", C.c_double)]
+
+
+class PeaksInfo(C.Structure):
+    """vsig_peaks_info_t (include/vsig.h)."""
+    _fields_ = [("count", I64), ("argmax", I64), ("max", C.c_double), ("thr_used", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/vsig.h declares.
 SIGNATURES = {
     "vsig_version": (C.c_int, []),
@@ -109,6 +120,9 @@ SIGNATURES = {
     "vsig_filter_channel_dev": (C.c_int, [P, I32, P, I64, C.c_double, C.c_double, C.c_double, P]),
     "vsig_peak_dev": (C.c_int, [P, I32, P, I64, P]),
     "vsig_peak": (C.c_int, [P, I32, P, I64, P]),
+    "vsig_peaks_tile": (C.c_int, []),
+    "vsig_peaks_dev": (C.c_int, [P, I32, P, I64, C.c_double, I32, I64, P, I64, P]),
+    "vsig_peaks": (C.c_int, [P, I32, P, I64, C.c_double, I32, I64, P, I64, P]),
     "vsig_abs_stats_dev": (C.c_int, [P, I32, P, I64, P]),
     "vsig_correlate_stats_dev": (C.c_int, [P, I32, P, I64, P, I64, I32, P]),
     "vsig_mix_c64_dev": (C.c_int, [P, P, I64, C.c_double, C.c_double, I64, P]),

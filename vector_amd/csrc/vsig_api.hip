@@ -88,6 +88,7 @@ struct vsig_ctx {
   DevBuf lkeys;                          // correlator lane keys (refine column candidates)
   DevBuf vscratch;                       // numpy-order |c| of every output (exact stats)
   DevBuf sscratch;                       // np_stats buffer sums
+  DevBuf pscratch;                       // peaks.hip tile table, counts, offsets
   PeakPartial* parts() const { return partials.as<PeakPartial>(); }
   // the first-level buffer of a two-level finalize, right after the partials,
   // then the fused finalize's block counters (zero between launches)
@@ -1407,6 +1408,65 @@ int vsig_peak(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, vsig_peak_t*
       (rc = stage_out(c, peak, c->result, sizeof(vsig_peak_t))))
     return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VSIG_OK;
+}
+
+// ---------------------------------------------------------------- peak list
+static_assert(sizeof(vsig_instance_t) == sizeof(vsig::PeakInst) && sizeof(vsig_instance_t) == 16,
+              "vsig_instance_t layout");
+static_assert(sizeof(vsig_peaks_info_t) == sizeof(vsig::PeaksInfo) && sizeof(vsig_peaks_info_t) == 32,
+              "vsig_peaks_info_t layout");
+
+int vsig_peaks_tile(void) { return vsig::kPeaksTile; }
+
+static int peaks_check(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, double thr,
+                       int64_t min_distance, const void* out, int64_t cap, const void* info) {
+  if (!c || !a || !info) return fail(c, VSIG_E_INVALID, "null pointer");
+  if (n < 1) return fail(c, VSIG_E_INVALID, "empty input");
+  if (n > (1LL << 40)) return fail(c, VSIG_E_INVALID, "n above 2^40");
+  if (dtype < VSIG_DTYPE_C128 || dtype > VSIG_DTYPE_F32) return fail(c, VSIG_E_INVALID, "dtype");
+  if (cap < 0 || min_distance < 0) return fail(c, VSIG_E_INVALID, "need cap >= 0 and min_distance >= 0");
+  if (cap > 0 && !out) return fail(c, VSIG_E_INVALID, "null out with cap > 0");
+  if (thr != thr) return fail(c, VSIG_E_INVALID, "thr is NaN");
+  return VSIG_OK;
+}
+
+int vsig_peaks_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, double thr, int32_t relative,
+                   int64_t min_distance, vsig_instance_t* out_dev, int64_t cap,
+                   vsig_peaks_info_t* info_dev) {
+  int rc = peaks_check(c, dtype, a, n, thr, min_distance, out_dev, cap, info_dev);
+  if (rc || (rc = c->pscratch.reserve(c, vsig::peaks_scratch_bytes(n)))) return rc;
+  Timed t(c, "peaks");
+  HIPCHK(c, vsig::launch_peaks(dtype, a, n, thr, relative != 0, min_distance,
+                               reinterpret_cast<vsig::PeakInst*>(out_dev), cap,
+                               reinterpret_cast<vsig::PeaksInfo*>(info_dev), c->pscratch.data(), c->stream));
+  return VSIG_OK;
+}
+
+int vsig_peaks(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, double thr, int32_t relative,
+               int64_t min_distance, vsig_instance_t* out, int64_t cap, vsig_peaks_info_t* info) {
+  int rc = peaks_check(c, dtype, a, n, thr, min_distance, out, cap, info);
+  if (rc) return rc;
+  const size_t es = dtype == VSIG_DTYPE_C128 ? 16 : (dtype == VSIG_DTYPE_F32 ? 4 : 8);
+  // stage[1]: the info record, then the instance records
+  const size_t ib = sizeof(vsig_peaks_info_t);
+  if ((rc = stage_in(c, 0, a, (size_t)n * es)) ||
+      (rc = c->stage[1].reserve(c, ib + (size_t)cap * sizeof(vsig_instance_t))))
+    return rc;
+  char* sb = c->stage[1].as<char>();
+  vsig_instance_t* od = cap > 0 ? reinterpret_cast<vsig_instance_t*>(sb + ib) : nullptr;
+  if ((rc = vsig_peaks_dev(c, dtype, c->stage[0].data(), n, thr, relative, min_distance, od, cap,
+                           reinterpret_cast<vsig_peaks_info_t*>(sb))))
+    return rc;
+  vsig_peaks_info_t h;
+  HIPCHK(c, hipMemcpyAsync(&h, sb, ib, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int64_t k = h.count < cap ? h.count : cap;
+  if (k > 0) {
+    HIPCHK(c, hipMemcpyAsync(out, od, (size_t)k * sizeof(vsig_instance_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  *info = h;
   return VSIG_OK;
 }
 

@@ -327,4 +327,16 @@ hipError_t launch_db_transform(int dtype, const void* a, long long n, double flo
 hipError_t launch_abs_c64(int dtype, const void* a, long long n, float2* out, hipStream_t st);
 hipError_t launch_abs_c128(int dtype, const void* a, long long n, double2* out, hipStream_t st);
 
+// peaks.hip: the peak list of |a| (threshold + first maximum of a +-d window;
+// see the file's header).  thr: absolute, or with `relative` a ratio of
+// max |a| multiplied on the device.  out: the first `cap` instances in
+// ascending index order (may be null when cap == 0); info: always written.
+// scratch: peaks_scratch_bytes(n).
+constexpr int kPeaksTile = 2048;
+struct PeakInst { long long index; double value; };                          // = vsig_instance_t
+struct PeaksInfo { long long count, argmax; double max, thr_used; };         // = vsig_peaks_info_t
+size_t peaks_scratch_bytes(long long n);
+hipError_t launch_peaks(int dtype, const void* a, long long n, double thr, int relative, long long d,
+                        PeakInst* out, long long cap, PeaksInfo* info, void* scratch, hipStream_t st);
+
 }  // namespace vsig

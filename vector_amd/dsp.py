@@ -32,7 +32,7 @@ from .windows import get_window
 __all__ = ["spectrum", "filter", "fir_filter", "correlate", "correlate_peak",
            "cross_correlate_signals", "find_correlation_peak",
            "find_packet_location_in_vector", "FirFilter", "Correlator", "peak_stats",
-           "refine_status", "check_refine"]
+           "refine_status", "check_refine", "find_peaks", "find_packet_instances"]
 
 PEAK_BYTES = 32  # sizeof(vsig_peak_t)
 
@@ -618,6 +618,130 @@ class Correlator:
                 self.h = None
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------
+# peak list — every instance, where find_correlation_peak stops at one argmax
+# ---------------------------------------------------------------------------
+def _check_peaks_args(threshold, min_distance, max_peaks):
+    if np.isnan(threshold):
+        raise ValueError("threshold must not be NaN")
+    if int(min_distance) < 0:
+        raise ValueError("min_distance must be >= 0")
+    if int(max_peaks) < 0:
+        raise ValueError("max_peaks must be >= 0")
+
+
+def _peaks_dev(t, code, threshold, min_distance, relative, max_peaks, ctx):
+    """vsig_peaks_dev on a contiguous CUDA tensor: (indices int64[max_peaks],
+    values float64[max_peaks], info int64[4]) on the device, nothing synchronised."""
+    n = int(t.numel())
+    if n == 0:
+        raise ValueError("attempt to get argmax of an empty sequence")
+    max_peaks = int(max_peaks)
+    rec = torch.empty((max_peaks, 2), dtype=torch.int64, device=t.device)
+    rec[:, 0] = -1
+    rec[:, 1] = 0
+    info = torch.empty(4, dtype=torch.int64, device=t.device)
+    ctx.check(ctx.lib.vsig_peaks_dev(ctx.h, _lib.DTYPES[code], _ptr(t), n, float(threshold),
+                                     1 if relative else 0, int(min_distance),
+                                     _ptr(rec) if max_peaks else None, max_peaks, _ptr(info)), "peaks")
+    return rec[:, 0].contiguous(), rec[:, 1].contiguous().view(torch.float64), info
+
+
+def _trim_peaks(idx, val, info, max_peaks, what):
+    """Host (indices, values) of a device peak list, cut at its count."""
+    count = int(info[0].item())
+    if count > max_peaks:
+        warnings.warn(f"{what}: {count} instances, the first {max_peaks} are returned",
+                      RuntimeWarning, stacklevel=3)
+    k = min(count, int(max_peaks))
+    return idx[:k].cpu().numpy(), val[:k].cpu().numpy()
+
+
+def find_peaks(a, threshold, min_distance=0, relative=False, max_peaks=65536):
+    """The peaks of ``m = |a|`` (complex or real, numpy's abs in a's precision):
+    every index i with ``m[i] >= threshold`` that is the first maximum of m
+    over ``[i - min_distance, i + min_distance]`` (clipped to the array), i.e.
+    ``lo + np.argmax(m[lo:hi+1]) == i`` -- in ascending order, found on the GPU
+    (vsig_peaks_dev).  relative=True: the threshold is ``threshold * max(m)``.
+
+    This is a maximum filter, not the greedy selection of
+    ``scipy.signal.find_peaks(distance=)``: a peak beaten by a higher
+    neighbour within min_distance is dropped even if that neighbour is itself
+    dropped.  Two peaks are more than min_distance apart; min_distance=0 keeps
+    every element at or above the threshold; a flat array has the one peak 0;
+    relative=True with threshold 1.0 returns np.argmax's index alone.  NaN
+    elements are outside the contract (they are never peaks and never
+    suppress one).
+
+    numpy in -> ``(indices int64[k], values float64[k])``; with more than
+    max_peaks peaks a RuntimeWarning and the first max_peaks.  CUDA tensor in
+    -> ``(indices, values, info)`` device tensors, nothing synchronised:
+    max_peaks entries each (-1 / 0 past the count), info = int64[4] holding
+    vsig_peaks_info_t (count, argmax; max and thr_used as float64 bits:
+    ``info.view(torch.float64)[2:]``)."""
+    _check_peaks_args(threshold, min_distance, max_peaks)
+    ctx = _lib.get_context()
+    if _is_dev(a):
+        if a.dim() != 1:
+            raise ValueError("vector_amd works on 1-D signals")
+        if not a.is_cuda:
+            a = a.to(f"cuda:{ctx.device}")
+    t, code = _stats_operand(a, ctx)
+    idx, val, info = _peaks_dev(t, code, threshold, min_distance, relative, max_peaks, ctx)
+    if _is_dev(a):
+        return idx, val, info
+    return _trim_peaks(idx, val, info, int(max_peaks), "find_peaks")
+
+
+def find_packet_instances(vector, packet, threshold_ratio=0.5, min_distance=None,
+                          max_instances=65536):
+    """Where every instance of ``packet`` starts in ``vector``:
+    ``c = np.correlate(vector, packet, 'valid')`` on the GPU, stored as
+    complex64 (no argmax refine runs), then ``find_peaks(c, threshold_ratio,
+    min_distance, relative=True)``.  A start is the index in ``vector`` of the
+    packet's first sample; min_distance defaults to ``len(packet) // 2``.
+
+    The values are |c| at complex64 accuracy (about 1e-5 relative of numpy's
+    complex128 correlation).  The threshold is relative to the stored array's
+    own maximum, so the call is self-consistent and does not depend on the
+    exact-argmax refine of the other correlation front ends.
+
+    numpy in -> ``(starts int64[k], values float64[k])`` (RuntimeWarning and
+    the first max_instances when there are more); CUDA tensors in -> device
+    tensors of max_instances entries, -1 / 0 past the count, nothing
+    synchronised.  ValueError when the vector is shorter than the packet or
+    either is empty."""
+    nv = int(vector.shape[0]) if _is_dev(vector) else len(vector)
+    npk = int(packet.shape[0]) if _is_dev(packet) else len(packet)
+    if nv == 0:
+        raise ValueError("a cannot be empty")
+    if npk == 0:
+        raise ValueError("v cannot be empty")
+    if nv < npk:
+        raise ValueError(f"vector ({nv} samples) shorter than the packet ({npk})")
+    d = npk // 2 if min_distance is None else int(min_distance)
+    _check_peaks_args(threshold_ratio, d, max_instances)
+    ctx = _lib.get_context()
+    vd, pd = _device_c64(vector, ctx), _device_c64(packet, ctx)
+    nout = nv - npk + 1
+    c = torch.empty(nout, dtype=torch.complex64, device=vd.device)
+    # the entry point refines its peak record whether or not the caller takes
+    # one; the stored array is all that is used here, so the refine is off
+    # for this one call
+    was = C.c_int()
+    ctx.check(ctx.lib.vsig_get_option(ctx.h, b"refine", C.byref(was)), "refine option")
+    ctx.check(ctx.lib.vsig_set_option(ctx.h, b"refine", 0), "refine option")
+    try:
+        ctx.check(ctx.lib.vsig_correlate_c64_dev(ctx.h, _ptr(vd), nv, _ptr(pd), npk,
+                                                 _lib.MODES["valid"], _ptr(c), None), "correlate")
+    finally:
+        ctx.check(ctx.lib.vsig_set_option(ctx.h, b"refine", was.value), "refine option")
+    idx, val, info = _peaks_dev(c, "c64", threshold_ratio, d, True, max_instances, ctx)
+    if _is_dev(vector) or _is_dev(packet):
+        return idx, val
+    return _trim_peaks(idx, val, info, int(max_instances), "find_packet_instances")
 
 
 def find_packet_location_in_vector(vector, packet_signal, reference_segment,

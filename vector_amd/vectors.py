@@ -31,12 +31,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dsp import _device_c64, _is_dev, _ptr, peak_stats
+from .dsp import _device_c64, _is_dev, _ptr, find_packet_instances, peak_stats
 
 __all__ = ["apply_frequency_shift", "resample_signal", "transplant_packet_in_vector", "mat2wv",
            "save_vector_wv",
            "load_packet", "load_packet_info", "save_vector", "read_mat", "write_mat_vector",
-           "VectorPlan", "vector_plan", "build_vector", "compute_freq_ranges"]
+           "VectorPlan", "vector_plan", "build_vector", "compute_freq_ranges",
+           "validate_packet_timing", "verify_vector"]
 
 
 def _as_out(t: torch.Tensor, like_dev: bool):
@@ -528,20 +529,11 @@ def vector_plan(configs, vector_length, sample_rate) -> VectorPlan:
     return _plan(configs, lengths, pres, vector_length, sample_rate)
 
 
-def build_vector(configs, vector_length, sample_rate, normalize=False, device=False):
-    """generate_vector (unified_gui.py:1692-1791) up to the save: every
-    packet loaded (``file``: load_packet_info; ``signal``: an array or device
-    tensor, with ``pre_samples``), resampled when its ``sample_rate`` differs
-    (main.py:236-237), mixed by ``freq_shift`` once (the phase restarts at
-    every instance) and added into a zeroed complex64 vector every ``period``
-    seconds from ``start_time`` -- one vsig_vector_build_dev, numpy's adds in
-    numpy's order -- then divided by its peak |v| on the device when
-    ``normalize`` (left as is when the peak is 0).  Returns (vector, markers):
-    a numpy array, or with device=True the tensor in HBM, ready for
-    save_vector / save_vector_wv / create_spectrogram."""
-    configs = list(configs)
-    _check_vector_args(configs, vector_length)
-    ctx = _lib.get_context()
+def _prepare_packets(configs, sample_rate, ctx):
+    """Every config's packet as generate_vector inserts it (device complex64)
+    and its pre_samples: loaded (``file``) or taken (``signal``), resampled
+    when its ``sample_rate`` differs (main.py:236-237), mixed by
+    ``freq_shift`` once.  Shared by build_vector and verify_vector."""
     packets, pres = [], []
     for cfg in configs:
         if cfg.get("signal") is not None:
@@ -556,6 +548,24 @@ def build_vector(configs, vector_length, sample_rate, normalize=False, device=Fa
             y = apply_frequency_shift(y, shift, sample_rate)
         packets.append(y.contiguous())
         pres.append(pre)
+    return packets, pres
+
+
+def build_vector(configs, vector_length, sample_rate, normalize=False, device=False):
+    """generate_vector (unified_gui.py:1692-1791) up to the save: every
+    packet loaded (``file``: load_packet_info; ``signal``: an array or device
+    tensor, with ``pre_samples``), resampled when its ``sample_rate`` differs
+    (main.py:236-237), mixed by ``freq_shift`` once (the phase restarts at
+    every instance) and added into a zeroed complex64 vector every ``period``
+    seconds from ``start_time`` -- one vsig_vector_build_dev, numpy's adds in
+    numpy's order -- then divided by its peak |v| on the device when
+    ``normalize`` (left as is when the peak is 0).  Returns (vector, markers):
+    a numpy array, or with device=True the tensor in HBM, ready for
+    save_vector / save_vector_wv / create_spectrogram."""
+    configs = list(configs)
+    _check_vector_args(configs, vector_length)
+    ctx = _lib.get_context()
+    packets, pres = _prepare_packets(configs, sample_rate, ctx)
     plan = _plan(configs, [int(y.shape[0]) for y in packets], pres, vector_length, sample_rate)
     n = plan.total_samples
     out = torch.empty(n, dtype=torch.complex64, device=f"cuda:{ctx.device}")
@@ -573,6 +583,148 @@ def build_vector(configs, vector_length, sample_rate, normalize=False, device=Fa
         ctx.check(ctx.lib.vsig_normalize_c64_dev(ctx.h, _ptr(out), n, _ptr(peak), _ptr(out)),
                   "normalize")
     return (out if device else out.cpu().numpy()), plan.markers
+
+
+def _timing_status(overall):
+    if overall > 99.5:
+        return "✅ PERFECT"
+    if overall > 99.0:
+        return "✅ EXCELLENT"
+    if overall > 95.0:
+        return "⚠️ GOOD"
+    if overall > 90.0:
+        return "⚠️ FAIR"
+    return "❌ POOR"
+
+
+def validate_packet_timing(markers, configs):
+    """The timing score of validate_packet_timing (unified_gui.py:1496-1690) as
+    a host function on plain config dicts (the keys build_vector takes; a
+    config's name is its file's base name, else ``name``, else packet_<i+1>),
+    so that measured markers (verify_vector) score like planned ones
+    (VectorPlan.markers).  Per named packet, marker times sorted:
+
+      start     |first time - start_time| in ms against a tolerance of 10 ms
+                (<= 2 instances) or 5 ms: 100 inside it, else
+                max(0, 100 - err / tol * 50)
+      period    e = |mean interval - period| / period * 100:  100 if e <= 1,
+                100 - (e - 1) * 5 if e <= 5, else max(0, 80 - (e - 5) * 2)
+      frequency always 100;  consistency 100, or 80 for a single instance
+      packet    0.4 period + 0.3 start + 0.2 frequency + 0.1 consistency,
+                + min(5, instances - 2) above 2 instances, capped at 100
+
+    Overall is the mean over packets.  Returns
+    ``(f"Timing Validation: {overall:.1f}% {status}", details)`` -- details:
+    one dict per packet (packet_name, instances, start_time_error_ms,
+    period_error_percent, freq_shift_mhz, explanations) -- or
+    ``("No packets to validate", [])``.  Prints nothing."""
+    by_name = {}
+    for time_sec, shift, name, _style, _colour in markers:
+        by_name.setdefault(name, []).append((time_sec, shift))
+    scores, details = [], []
+    for idx, cfg in enumerate(configs):
+        if not cfg:
+            continue
+        name = _base_name(cfg, idx)
+        if name not in by_name:
+            continue
+        found = sorted(by_name[name], key=lambda m: m[0])
+        times = [m[0] for m in found]
+        shifts = [m[1] for m in found]
+        count = len(times)
+        period_ms = cfg["period"] * 1000
+        want_shift = cfg.get("freq_shift", 0)
+
+        start_err = abs(times[0] * 1000 - cfg["start_time"] * 1000)
+        tol = 10.0 * (1.0 if count <= 2 else 0.5)
+        if start_err <= tol:
+            start_acc, start_txt = 100.0, f"start within tolerance ({start_err:.2f} ms off)"
+        else:
+            start_acc = max(0, 100 - (start_err / tol * 50))
+            start_txt = f"start outside tolerance ({start_err:.2f} ms off)"
+
+        period_acc, period_err, period_txt = 100.0, 0.0, ""
+        if count > 1:
+            gaps = [(times[i] - times[i - 1]) * 1000 for i in range(1, count)]
+            avg, std = np.mean(gaps), np.std(gaps)
+            period_err = abs(avg - period_ms) / period_ms * 100
+            if period_err <= 1.0:
+                period_txt = f"period on target (mean {avg:.2f} ms, std {std:.2f} ms)"
+            elif period_err <= 5.0:
+                period_acc = 100 - (period_err - 1.0) * 5
+                period_txt = f"period close (mean {avg:.2f} ms, {period_err:.1f}% off)"
+            else:
+                period_acc = max(0, 80 - (period_err - 5.0) * 2)
+                period_txt = f"period off target (mean {avg:.2f} ms, {period_err:.1f}% off)"
+        else:
+            period_txt = "one instance: no period to check"
+
+        distinct = set(shifts)
+        if len(distinct) > 1:
+            freq_txt = f"{len(distinct)} different frequency shifts"
+        elif shifts[0] == want_shift:
+            freq_txt = f"frequency shift as configured ({want_shift / 1e6:.1f} MHz)"
+        else:
+            freq_txt = (f"frequency shift {shifts[0] / 1e6:.1f} MHz, configured "
+                        f"{want_shift / 1e6:.1f} MHz")
+
+        if count >= 2:
+            cons_acc, cons_txt = 100.0, f"{count} instances"
+        else:
+            cons_acc, cons_txt = 80.0, "one instance: consistency cannot be checked"
+
+        acc = period_acc * 0.4 + start_acc * 0.3 + 100.0 * 0.2 + cons_acc * 0.1
+        if count > 2:
+            acc = min(100.0, acc + min(5.0, (count - 2) * 1.0))
+        scores.append(acc)
+        details.append({
+            "packet_name": name,
+            "instances": count,
+            "start_time_error_ms": start_err,
+            "period_error_percent": period_err if count > 1 else 0,
+            "freq_shift_mhz": want_shift / 1e6,
+            "explanations": {"start": start_txt, "period": period_txt, "freq": freq_txt,
+                             "consistency": cons_txt},
+        })
+    if not scores:
+        return "No packets to validate", []
+    overall = sum(scores) / len(scores)
+    return f"Timing Validation: {overall:.1f}% {_timing_status(overall)}", details
+
+
+def verify_vector(vector, configs, vector_length, sample_rate, threshold_ratio=0.5):
+    """Where every configured packet really sits in ``vector`` (a numpy array
+    or a device tensor, e.g. build_vector's output or a capture), and how that
+    timing scores.  Each config's packet is prepared exactly as build_vector
+    inserts it (loaded, resampled, mixed), correlated over the vector and its
+    instances listed (dsp.find_packet_instances at ``threshold_ratio`` of the
+    strongest, min_distance = min(len(packet), period_samples) // 2).  Returns
+    ``(measured_markers, validate_packet_timing(measured_markers, configs))``;
+    a measured marker is ((start + pre_samples) / sample_rate, freq_shift,
+    name, style, colour), the layout and order of VectorPlan.markers."""
+    configs = list(configs)
+    _check_vector_args(configs, vector_length)
+    ctx = _lib.get_context()
+    packets, pres = _prepare_packets(configs, sample_rate, ctx)
+    vd = _device_c64(vector.reshape(-1) if _is_dev(vector) else np.asarray(vector).ravel(), ctx)
+    markers, styles = [], {}
+    for idx, (cfg, y, pre) in enumerate(zip(configs, packets, pres)):
+        name = _base_name(cfg, idx)
+        if name not in styles:
+            styles[name] = (_MARKER_STYLES[len(styles) % len(_MARKER_STYLES)],
+                            _MARKER_COLORS[len(styles) % len(_MARKER_COLORS)])
+        style, color = styles[name]
+        period_samples = int(cfg["period"] * sample_rate)
+        if period_samples <= 0:
+            raise ValueError(f"Invalid period for packet {idx + 1}")
+        n = int(y.shape[0])
+        if n == 0 or n > int(vd.shape[0]):
+            continue
+        starts, _ = find_packet_instances(vd, y, threshold_ratio, min(n, period_samples) // 2)
+        starts = starts[starts >= 0].cpu().tolist()
+        shift = cfg.get("freq_shift", 0)
+        markers.extend(((s + pre) / sample_rate, shift, name, style, color) for s in starts)
+    return markers, validate_packet_timing(markers, configs)
 
 
 def compute_freq_ranges(shifts, margin=1e6):
