@@ -283,6 +283,15 @@ int vsig_abs_stats_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, d
  * correlators' fp32 sums cannot resolve numpy's rounding-noise std. */
 int vsig_correlate_stats_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t na, const void* v,
                              int64_t nv, int32_t mode, double* stats_dev);
+/* validate_transplant_quality's three mean powers (utils.py:1546-1552) in one
+ * pass over two complex64 regions: sums_dev = device double[3] =
+ * { sum |a|^2, sum |b|^2, sum |a-b|^2 }, each |.|^2 formed in float32 as numpy
+ * forms np.abs(x)**2, summed in double in a fixed order.  Enqueued on the
+ * context stream, no synchronisation; the same operands give the same bits on
+ * every run.  a and b are 8-byte aligned (any slice of a complex64 array) and
+ * may be the same array.  n < 1, a NULL pointer or an operand off an 8-byte
+ * boundary: VSIG_E_INVALID. */
+int vsig_region_power_dev(vsig_ctx* ctx, const void* a, const void* b, int64_t n, double* sums_dev);
 
 /* ---- stream ops either side of the chain.
  * vsig_mix_c64_dev: y[i] = x[i] * exp(j w (i0 + i) / sr) — apply_frequency_shift

@@ -16,6 +16,8 @@ from .spectrogram import create_spectrogram, spectrogram_params  # noqa: F401
 from .channelizer import Channelizer, filter_channel, pfb_channelize  # noqa: F401
 from .vectors import (apply_frequency_shift, resample_signal, load_packet, load_packet_info, mat2wv,  # noqa: F401
                       save_vector, save_vector_wv, transplant_packet_in_vector,
+                      extract_reference_segment, measure_packet_timing, validate_transplant_quality,
+                      transplant_and_validate,
                       VectorPlan, build_vector, compute_freq_ranges, validate_packet_timing, vector_plan,
                       verify_vector)
 from .analysis import (boxcar_energy, detect_packet_bounds, find_packet_start,  # noqa: F401

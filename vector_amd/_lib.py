@@ -125,6 +125,7 @@ SIGNATURES = {
     "vsig_peaks": (C.c_int, [P, I32, P, I64, C.c_double, I32, I64, P, I64, P]),
     "vsig_abs_stats_dev": (C.c_int, [P, I32, P, I64, P]),
     "vsig_correlate_stats_dev": (C.c_int, [P, I32, P, I64, P, I64, I32, P]),
+    "vsig_region_power_dev": (C.c_int, [P, P, P, I64, P]),
     "vsig_mix_c64_dev": (C.c_int, [P, P, I64, C.c_double, C.c_double, I64, P]),
     "vsig_scale_c64_dev": (C.c_int, [P, P, I64, C.c_float, P]),
     "vsig_wv_quantize_dev": (C.c_int, [P, P, I64, C.c_float, P]),

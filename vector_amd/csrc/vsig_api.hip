@@ -89,6 +89,7 @@ struct vsig_ctx {
   DevBuf vscratch;                       // numpy-order |c| of every output (exact stats)
   DevBuf sscratch;                       // np_stats buffer sums
   DevBuf pscratch;                       // peaks.hip tile table, counts, offsets
+  DevBuf gscratch;                       // region.hip per-block partials
   PeakPartial* parts() const { return partials.as<PeakPartial>(); }
   // the first-level buffer of a two-level finalize, right after the partials,
   // then the fused finalize's block counters (zero between launches)
@@ -1467,6 +1468,20 @@ int vsig_peaks(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, double thr,
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   *info = h;
+  return VSIG_OK;
+}
+
+// ---------------------------------------------------------------- region powers
+int vsig_region_power_dev(vsig_ctx* c, const void* a, const void* b, int64_t n, double* sums_dev) {
+  if (!c || !a || !b || !sums_dev) return fail(c, VSIG_E_INVALID, "null pointer");
+  if (n < 1) return fail(c, VSIG_E_INVALID, "empty input");  // the mean of an empty region
+  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 7)
+    return fail(c, VSIG_E_INVALID, "region power: operands must be 8-byte aligned");
+  int rc = c->gscratch.reserve(c, vsig::region_scratch_bytes());
+  if (rc) return rc;
+  Timed t(c, "region_power");
+  HIPCHK(c, vsig::launch_region_power(static_cast<const float2*>(a), static_cast<const float2*>(b), n,
+                                      sums_dev, c->gscratch.data(), c->stream));
   return VSIG_OK;
 }
 

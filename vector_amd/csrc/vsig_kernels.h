@@ -237,6 +237,15 @@ hipError_t launch_refine_values(const RefineArgs& r, long long lo, long long hi,
 size_t np_stats_scratch_bytes(long long n);
 hipError_t launch_np_stats(int dtype, const void* a, long long n, double* out, void* scratch,
                            hipStream_t st);
+// region.hip: sums[0..2] (device) = sum |a|^2, sum |b|^2, sum |a - b|^2 over two
+// complex64 regions of n samples, each term numpy's float32 np.abs(x) ** 2,
+// summed in double in a fixed order (one partial a block, at most
+// kRegionBlocks of them; scratch: region_scratch_bytes()).  a and b are
+// 8-byte aligned and may be the same array.
+constexpr int kRegionBlocks = 2048;
+size_t region_scratch_bytes();
+hipError_t launch_region_power(const float2* a, const float2* b, long long n, double* sums,
+                               void* scratch, hipStream_t st);
 hipError_t launch_convert_c(int to128, const void* x, long long n, void* y, hipStream_t st);
 
 // bigfft.hip: four-step FFT of M = N1 N2 > 16384 points, Bluestein for any

@@ -3,6 +3,10 @@
 
   apply_frequency_shift        utils.py:120-127            mix_c64 kernel
   transplant_packet_in_vector  utils.py:1437-1501          |x|^2 sums + scale_c64
+  extract_reference_segment    utils.py:1345-1369          host (a slice)
+  measure_packet_timing        utils.py:827-846            find_packet_start
+  validate_transplant_quality  utils.py:1504-1591          correlate_peak + region_power kernel
+  transplant_and_validate      unified_gui.py:1087-1233    the four transplant steps in one call
   mat2wv / save_vector_wv      mat_to_wv_converter.py:7-64, utils.py:672-677
                                                            wv_quantize kernel
   load_packet / load_packet_info / save_vector
@@ -31,10 +35,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dsp import _device_c64, _is_dev, _ptr, find_packet_instances, peak_stats
+from .analysis import find_packet_start
+from .dsp import (_device_c64, _is_dev, _ptr, correlate_peak, find_packet_instances,
+                  find_packet_location_in_vector, peak_stats)
 
-__all__ = ["apply_frequency_shift", "resample_signal", "transplant_packet_in_vector", "mat2wv",
-           "save_vector_wv",
+__all__ = ["apply_frequency_shift", "resample_signal", "transplant_packet_in_vector",
+           "extract_reference_segment", "measure_packet_timing", "validate_transplant_quality",
+           "transplant_and_validate", "mat2wv", "save_vector_wv",
            "load_packet", "load_packet_info", "save_vector", "read_mat", "write_mat_vector",
            "VectorPlan", "vector_plan", "build_vector", "compute_freq_ranges",
            "validate_packet_timing", "verify_vector"]
@@ -158,6 +165,147 @@ def transplant_packet_in_vector(vector, packet_signal, vector_location, packet_l
                                              float(scale) if scale is not None else 1.0, _ptr(dst)),
                   "scale")
     return _as_out(new, dev_in)
+
+
+# ---------------------------------------------------------------------------
+# the transplant workflow's other steps — utils.py:1345-1369, 827-846, 1504-1591
+# ---------------------------------------------------------------------------
+def extract_reference_segment(signal, start_sample, end_sample):
+    """utils.py:1345-1369: signal[max(0, start_sample):min(len(signal),
+    end_sample)] (a view; numpy arrays and device tensors alike), ValueError
+    for an empty range.  Host only: no device, no library."""
+    start_sample = max(0, start_sample)
+    end_sample = min(len(signal), end_sample)
+    if start_sample >= end_sample:
+        raise ValueError("Invalid sample range: start_sample >= end_sample")
+    return signal[start_sample:end_sample]
+
+
+def measure_packet_timing(signal, template=None):
+    """utils.py:827-846: (pre_samples, post_samples, packet_start) around
+    find_packet_start's packet_start; post_samples is 0 without a template."""
+    packet_start = find_packet_start(signal, template)
+    pre_samples = packet_start
+    post_samples = len(signal) - packet_start - len(template) if template is not None else 0
+    return pre_samples, post_samples, packet_start
+
+
+def _region_c64(vector, lo, hi, ctx, what):
+    """vector[lo:hi] (Python slicing) of a complex64 vector as a device tensor;
+    a host vector uploads the region alone."""
+    if _is_dev(vector):
+        if vector.dtype != torch.complex64 or vector.dim() != 1:
+            raise NotImplementedError(f"{what}: complex64 vectors only")
+        t = vector[lo:hi]
+        return (t if t.is_cuda else t.to(f"cuda:{ctx.device}")).contiguous()
+    va = np.asarray(vector)
+    if va.dtype != np.complex64 or va.ndim != 1:
+        raise NotImplementedError(f"{what}: complex64 vectors only")
+    return torch.from_numpy(np.ascontiguousarray(va[lo:hi])).to(f"cuda:{ctx.device}")
+
+
+def _region_powers(a: torch.Tensor, b: torch.Tensor, ctx):
+    """(mean |a|^2, mean |b|^2, mean |a - b|^2) of two complex64 regions as the
+    float32 numpy's means return: one pass on the GPU (region.hip: numpy's
+    float32 element values, summed in double), one copy of three doubles."""
+    n = int(a.shape[0])
+    sums = torch.empty(3, dtype=torch.float64, device=a.device)
+    ctx.bind_stream()
+    ctx.check(ctx.lib.vsig_region_power_dev(ctx.h, _ptr(a), _ptr(b), n, _ptr(sums)), "region power")
+    return tuple(np.float32(s / n) for s in sums.cpu().tolist())
+
+
+def validate_transplant_quality(original_vector, transplanted_vector, packet_signal,
+                                vector_location, reference_segment, sample_rate):
+    """utils.py:1504-1591: the same dict (keys, nested ``criteria``, thresholds
+    0.3 / 0.01 / -30) scored on the GPU.  Both regions are
+    ``vector[vector_location:transplant_end]`` as the reference slices them
+    (a negative location follows Python slicing); the correlation with
+    ``reference_segment`` is correlate_peak (never stored), the three mean
+    powers come from one pass over both regions (vsig_region_power_dev), each
+    rounded to the float32 numpy's mean returns, and the reference's
+    expressions are evaluated on those scalars.  complex64 vectors, numpy
+    arrays or device tensors (the same dict either way); ``packet_signal``
+    counts for its length only.
+
+    ValueError for an empty region -- the reference raises it through
+    np.correlate when ``reference_segment`` is not empty and would go on to the
+    mean of an empty slice (nan, with a warning) when it is; both raise here --
+    and for regions of different lengths (numpy's broadcast error)."""
+    ctx = _lib.get_context()
+    what = "validate_transplant_quality"
+    transplant_end = min(vector_location + len(packet_signal), len(transplanted_vector))
+    transplant_length = transplant_end - vector_location
+    lo, hi = int(vector_location), int(transplant_end)
+    transplanted_region = _region_c64(transplanted_vector, lo, hi, ctx, what)
+    original_region = _region_c64(original_vector, lo, hi, ctx, what)
+    n = int(transplanted_region.shape[0])
+
+    if len(reference_segment) > 0:
+        _, ref_peak_val, ref_confidence = correlate_peak(reference_segment, transplanted_region)
+    else:
+        ref_confidence = 0.0
+        ref_peak_val = 0.0
+    if n == 0:
+        raise ValueError(f"{what}: empty transplant region")
+    if int(original_region.shape[0]) != n:
+        raise ValueError(f"operands could not be broadcast together with shapes "
+                         f"({int(original_region.shape[0])},) ({n},)")
+
+    original_power, transplanted_power, noise_power = _region_powers(
+        original_region, transplanted_region, ctx)
+    power_ratio = transplanted_power / original_power if original_power > 0 else 0.0
+    signal_power = transplanted_power
+    snr_improvement = 10 * np.log10(signal_power / noise_power) if noise_power > 0 else np.inf
+
+    time_precision_us = 1e6 / sample_rate
+    confidence_threshold = 0.3
+    power_ratio_threshold = 0.01
+    min_snr_threshold = -30
+    confidence_ok = ref_confidence > confidence_threshold
+    power_ok = power_ratio > power_ratio_threshold
+    snr_ok = snr_improvement > min_snr_threshold
+    success = confidence_ok and power_ok and snr_ok
+    return {
+        'reference_correlation': ref_peak_val,
+        'reference_confidence': ref_confidence,
+        'power_ratio': power_ratio,
+        'snr_improvement_db': snr_improvement,
+        'transplant_length_samples': transplant_length,
+        'transplant_length_us': transplant_length * 1e6 / sample_rate,
+        'time_precision_us': time_precision_us,
+        'vector_location': vector_location,
+        'success': success,
+        'criteria': {
+            'confidence_ok': confidence_ok,
+            'power_ok': power_ok,
+            'snr_ok': snr_ok,
+            'confidence_threshold': confidence_threshold,
+            'power_ratio_threshold': power_ratio_threshold,
+            'min_snr_threshold': min_snr_threshold,
+        },
+    }
+
+
+def transplant_and_validate(vector, packet_signal, ref_start, ref_end, sample_rate,
+                            search_window=None, correlation_threshold=0.5):
+    """The transplant tab's sequence (unified_gui.py:1087-1233) in one call:
+    extract_reference_segment(packet_signal, ref_start, ref_end),
+    find_packet_location_in_vector, transplant_packet_in_vector at the location
+    found (packet_location as returned, normalize_power=True) and
+    validate_transplant_quality.  Returns (new_vector, location, validation),
+    location = dict(vector_location, packet_location, confidence).  A device
+    ``vector`` keeps everything but the scalar results on the device."""
+    reference_segment = extract_reference_segment(packet_signal, ref_start, ref_end)
+    vector_location, packet_location, confidence = find_packet_location_in_vector(
+        vector, packet_signal, reference_segment, search_window, correlation_threshold)
+    new_vector = transplant_packet_in_vector(vector, packet_signal, vector_location,
+                                             packet_location, normalize_power=True)
+    validation = validate_transplant_quality(vector, new_vector, packet_signal, vector_location,
+                                             reference_segment, sample_rate)
+    location = dict(vector_location=vector_location, packet_location=packet_location,
+                    confidence=confidence)
+    return new_vector, location, validation
 
 
 # ---------------------------------------------------------------------------
