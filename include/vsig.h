@@ -370,6 +370,43 @@ int vsig_db_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, double f
 int vsig_abs_c64_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, void* out);
 int vsig_abs_c128_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, void* out);
 
+/* ---- display image: the pixels the reference's three plot sites draw --
+ * plot_spectrogram (utils.py:429-449, 491-499: percentiles 5 / 95, the
+ * (2, 1) median filter, turbo / inferno), adjust_packet_bounds_gui
+ * (utils.py:1017-1022, 1062: 10 / 95, viridis, rows flipped) and
+ * vector_analyzer/spectrogram_analysis.py:56-62 (10 / 95, viridis) -- from
+ * Sxx in one pass, with no dB map in between.
+ * sxx: n_freq x n_time values of dtype VSIG_DTYPE_F32 or VSIG_DTYPE_F64;
+ *   freq_fast != 0: frame-major memory, element (i, j) at sxx[j*ld + i]
+ *   (ld >= n_freq); freq_fast == 0: C-contiguous, (i, j) at sxx[i*ld + j]
+ *   (ld >= n_time).  ld counts elements, so a slice along either axis is
+ *   rendered in place.  Rows that start on 16-byte boundaries (base and
+ *   ld * itemsize multiples of 16) are read with 16-byte loads.
+ * Pixel (r, c) of the ceil(n_freq / pool_f) x ceil(n_time / pool_t) image:
+ *   P  = max |sxx(i, j)| over i in [max(r*pool_f - (median != 0), 0),
+ *        min((r+1)*pool_f, n_freq)), j in [c*pool_t, min((c+1)*pool_t, n_time))
+ *        (the median filter of size (2, 1) is the maximum of rows i-1 and i,
+ *        row 0 with itself; peak-hold pooling has no reference counterpart);
+ *        a NaN anywhere in the window makes P NaN;
+ *   db = 10 log10(P + floor), rounded as vsig_db_dev rounds it;
+ *   xa = (db - vmin) / (vmax - vmin) * 256 in the input's dtype (matplotlib's
+ *        Normalize); table row: bad if xa is NaN, under if xa < 0, 255 if
+ *        xa == 256, over if xa > 256, else trunc(xa) (Colormap.__call__).
+ * lut_dev: 259 x 4 bytes on the device -- rows 0..255, under, over, bad
+ *   (matplotlib's _lut order); rgba_dev: rows * cols * 4 bytes, C-contiguous
+ *   [rows][cols][4]; with flip_freq output row r holds frequency block
+ *   rows - 1 - r.  Both 4-byte aligned.
+ * Enqueued on the context stream, no synchronisation; the same input gives
+ * the same bytes on every run.  A NULL pointer, an extent or pool factor
+ * below 1, ld below the fast extent, another dtype, a misaligned table or
+ * image, vmax <= vmin (also after rounding to float for F32) or a level that
+ * is not finite: VSIG_E_INVALID. */
+int vsig_spectrogram_image_dev(vsig_ctx* ctx, int32_t dtype, const void* sxx, int64_t n_freq,
+                               int64_t n_time, int32_t freq_fast, int64_t ld, double floor_,
+                               double vmin, double vmax, int32_t median, int32_t flip_freq,
+                               int32_t pool_f, int32_t pool_t, const uint8_t* lut_dev,
+                               uint8_t* rgba_dev);
+
 /* ---- peak list: every packet instance in a stored correlation (or the peaks
  * of any array of dtype VSIG_DTYPE_*), where the entry points above stop at
  * the one global argmax.  With m[i] = |a[i]| as vsig_peak_dev forms it

@@ -22,5 +22,7 @@ from .vectors import (apply_frequency_shift, resample_signal, load_packet, load_
                       verify_vector)
 from .analysis import (boxcar_energy, detect_packet_bounds, find_packet_start,  # noqa: F401
                        normalize_spectrogram, order_statistics, threshold_stats)
+from .display import (SpectrogramImage, colormap_table, image_extent, plot_spectrogram_image,  # noqa: F401
+                      pool_factors, spectrogram_image, spectrogram_levels)
 
 __version__ = "0.1.0"

@@ -141,6 +141,8 @@ SIGNATURES = {
     "vsig_db_dev": (C.c_int, [P, I32, P, I64, C.c_double, P]),
     "vsig_abs_c64_dev": (C.c_int, [P, I32, P, I64, P]),
     "vsig_abs_c128_dev": (C.c_int, [P, I32, P, I64, P]),
+    "vsig_spectrogram_image_dev": (C.c_int, [P, I32, P, I64, I64, I32, I64, C.c_double, C.c_double,
+                                             C.c_double, I32, I32, I32, I32, P, P]),
     "vsig_chain_create": (C.c_int, [P, C.POINTER(ChainConfig), I32, I32, C.POINTER(Transport),
                                     C.POINTER(P)]),
     "vsig_chain_free": (None, [P]),

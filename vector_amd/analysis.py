@@ -1,7 +1,7 @@
 """Detection / display helpers of the reference on the GPU (SURVEY.md §8(a)
 rows a3, a7, a8):
 
-  normalize_spectrogram   utils.py:356-404
+  normalize_spectrogram   utils.py:356-404  (spectrogram_levels: its level selection alone)
   find_packet_start       utils.py:784-809
   detect_packet_bounds    utils.py:811-825
 
@@ -22,7 +22,7 @@ import torch
 from . import _lib
 from .dsp import _correlate_dev, _is_dev, _ptr
 
-__all__ = ["normalize_spectrogram", "find_packet_start", "detect_packet_bounds",
+__all__ = ["normalize_spectrogram", "spectrogram_levels", "find_packet_start", "detect_packet_bounds",
            "order_statistics", "threshold_stats", "boxcar_energy"]
 
 _TORCH_CODE = {torch.complex128: "c128", torch.complex64: "c64", torch.float64: "f64",
@@ -159,21 +159,15 @@ def _median(n, dt, fetch):
 # ---------------------------------------------------------------------------
 # normalize_spectrogram — utils.py:356-404
 # ---------------------------------------------------------------------------
-def normalize_spectrogram(Sxx, low_percentile=10.0, high_percentile=95.0, max_dynamic_range=25):
-    """utils.py:356-404: (Sxx_db, vmin, vmax) with Sxx_db = 10 log10(|S| + floor),
-    floor = max(5th percentile of the positive |S|, 1e-12), vmin / vmax the
-    10th / 95th percentiles of Sxx_db, then the dynamic-range clamps.
-
-    The percentiles come from radix-select order statistics of |S| on the GPU:
-    10 log10(. + floor) is non-decreasing, so the k-th smallest dB value is
-    the transform of the k-th smallest |S|.  numpy in -> numpy out; a CUDA
-    tensor in -> Sxx_db stays on the device."""
+def _select_levels(Sxx, low_percentile, high_percentile, max_dynamic_range):
+    """The selection half of normalize_spectrogram (utils.py:363-402) for a
+    non-empty Sxx: the noise floor and vmin / vmax from order statistics of |S|,
+    with no dB map.  Returns (ctx, t, code, src, transposed, floor_v, db_dt,
+    vmin, vmax): t the flat device array the statistics were taken over (in the
+    storage order of src, which is Sxx or its transpose), db_dt the dtype numpy
+    evaluates the dB map in."""
     dev_in = _is_dev(Sxx)
-    size = int(Sxx.numel()) if dev_in else int(np.size(Sxx))
-    if size == 0:
-        return np.array([]), 0, 0
     ctx = _lib.get_context()
-    shape = tuple(Sxx.shape)
     # transposed views (spectrum() returns (nfft, frames) over frame-major
     # memory) are reduced in their storage order and returned in the same view
     src = Sxx
@@ -204,12 +198,6 @@ def normalize_spectrogram(Sxx, low_percentile=10.0, high_percentile=95.0, max_dy
     # numpy's promotion of |S| + noise_floor (NEP 50: a Python float is weak)
     db_dt = np.result_type(np.empty(0, dt), noise_floor)
     floor_v = float(np.asarray(noise_floor, dtype=db_dt))
-    out_t = torch.float32 if db_dt == np.float32 else torch.float64
-    if db_dt == np.float64 and code == "f32":
-        t = t.to(torch.float64)
-        code = "f64"
-    db = torch.empty(n, dtype=out_t, device=t.device)
-    ctx.check(ctx.lib.vsig_db_dev(ctx.h, _lib.DTYPES[code], _ptr(t), n, floor_v, _ptr(db)), "db")
 
     def db_of(v):
         return 10 * np.log10(np.asarray(v, dtype=db_dt) + np.asarray(floor_v, dtype=db_dt))
@@ -237,6 +225,45 @@ def normalize_spectrogram(Sxx, low_percentile=10.0, high_percentile=95.0, max_dy
     if actual_range != vmax - vmin:
         print(f"📊 Dynamic range adjusted: {actual_range:.1f}dB → {vmax - vmin:.1f}dB "
               "(optimized for resolution)")
+    return ctx, t, code, src, transposed, floor_v, db_dt, vmin, vmax
+
+
+def spectrogram_levels(Sxx, low_percentile=10.0, high_percentile=95.0, max_dynamic_range=25):
+    """(floor, vmin, vmax) of normalize_spectrogram (utils.py:356-404) without
+    its dB map: floor = max(5th percentile of the positive |S|, 1e-12), vmin /
+    vmax the percentiles of 10 log10(|S| + floor) after the dynamic-range
+    clamps, typed as the reference's.  An empty Sxx gives (0.0, 0, 0)."""
+    size = int(Sxx.numel()) if _is_dev(Sxx) else int(np.size(Sxx))
+    if size == 0:
+        return 0.0, 0, 0
+    _, _, _, _, _, floor_v, _, vmin, vmax = _select_levels(Sxx, low_percentile, high_percentile,
+                                                          max_dynamic_range)
+    return floor_v, vmin, vmax
+
+
+def normalize_spectrogram(Sxx, low_percentile=10.0, high_percentile=95.0, max_dynamic_range=25):
+    """utils.py:356-404: (Sxx_db, vmin, vmax) with Sxx_db = 10 log10(|S| + floor),
+    floor = max(5th percentile of the positive |S|, 1e-12), vmin / vmax the
+    10th / 95th percentiles of Sxx_db, then the dynamic-range clamps.
+
+    The percentiles come from radix-select order statistics of |S| on the GPU:
+    10 log10(. + floor) is non-decreasing, so the k-th smallest dB value is
+    the transform of the k-th smallest |S|.  numpy in -> numpy out; a CUDA
+    tensor in -> Sxx_db stays on the device."""
+    dev_in = _is_dev(Sxx)
+    size = int(Sxx.numel()) if dev_in else int(np.size(Sxx))
+    if size == 0:
+        return np.array([]), 0, 0
+    shape = tuple(Sxx.shape)
+    ctx, t, code, src, transposed, floor_v, db_dt, vmin, vmax = _select_levels(
+        Sxx, low_percentile, high_percentile, max_dynamic_range)
+    n = int(t.numel())
+    out_t = torch.float32 if db_dt == np.float32 else torch.float64
+    if db_dt == np.float64 and code == "f32":
+        t = t.to(torch.float64)
+        code = "f64"
+    db = torch.empty(n, dtype=out_t, device=t.device)
+    ctx.check(ctx.lib.vsig_db_dev(ctx.h, _lib.DTYPES[code], _ptr(t), n, floor_v, _ptr(db)), "db")
     if transposed:
         db = db.reshape(tuple(src.shape)).t()
     else:

@@ -18,6 +18,7 @@
 
 #include "vsig_kernels.h"
 #include "npabs.hpp"
+#include "dbmath.hpp"
 
 namespace vsig {
 
@@ -233,20 +234,19 @@ __global__ __launch_bounds__(256) void boxcar_same(const double* __restrict__ P,
 
 // ---------------------------------------------------------------- dB / abs
 // normalize_spectrogram's 10 * np.log10(|S| + floor) in the dtype numpy
-// evaluates it in (float32 S with a float32 floor stays float32).  The
-// float32 log10 is correctly rounded here; numpy's SIMD log10f is within a
-// few ulp of that, so dB maps agree to a few ulp (not bit-exact).
+// evaluates it in (float32 S with a float32 floor stays float32): db_of
+// (dbmath.hpp; dB maps agree with numpy's to a few ulp, not bit-exact).
 __global__ __launch_bounds__(256) void db_transform_f64(const double* __restrict__ a, long long n,
                                                         double floor_, double* __restrict__ out) {
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-    out[i] = 10.0 * log10(__dadd_rn(fabs(a[i]), floor_));
+    out[i] = db_of(a[i], floor_);
 }
 __global__ __launch_bounds__(256) void db_transform_f32(const float* __restrict__ a, long long n,
                                                         float floor_, float* __restrict__ out) {
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-    out[i] = __fmul_rn(10.f, (float)log10((double)__fadd_rn(fabsf(a[i]), floor_)));
+    out[i] = db_of(a[i], floor_);
 }
 
 // |a| + 0j (np.abs as numpy computes it: complex -> np_cabs, real -> fabs),

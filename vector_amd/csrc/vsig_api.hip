@@ -1763,4 +1763,32 @@ int vsig_abs_c128_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, void
   return VSIG_OK;
 }
 
+// ---------------------------------------------------------------- display image
+int vsig_spectrogram_image_dev(vsig_ctx* c, int32_t dtype, const void* sxx, int64_t n_freq,
+                               int64_t n_time, int32_t freq_fast, int64_t ld, double floor_,
+                               double vmin, double vmax, int32_t median, int32_t flip_freq,
+                               int32_t pool_f, int32_t pool_t, const uint8_t* lut_dev,
+                               uint8_t* rgba_dev) {
+  if (!c || !sxx || !lut_dev || !rgba_dev) return fail(c, VSIG_E_INVALID, "null pointer");
+  if (dtype != VSIG_DTYPE_F32 && dtype != VSIG_DTYPE_F64)
+    return fail(c, VSIG_E_INVALID, "spectrogram image: dtype must be VSIG_DTYPE_F32 or VSIG_DTYPE_F64");
+  if (n_freq < 1 || n_time < 1) return fail(c, VSIG_E_INVALID, "empty input");
+  if (pool_f < 1 || pool_t < 1) return fail(c, VSIG_E_INVALID, "spectrogram image: pool factors must be >= 1");
+  if (ld < (freq_fast ? n_freq : n_time))
+    return fail(c, VSIG_E_INVALID, "spectrogram image: ld is below the fast extent");
+  if ((reinterpret_cast<uintptr_t>(lut_dev) | reinterpret_cast<uintptr_t>(rgba_dev)) & 3)
+    return fail(c, VSIG_E_INVALID, "spectrogram image: table and image must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(sxx) & (dtype == VSIG_DTYPE_F32 ? 3 : 7))
+    return fail(c, VSIG_E_INVALID, "spectrogram image: sxx is not aligned to its dtype");
+  if (!std::isfinite(vmin) || !std::isfinite(vmax) || !(vmax > vmin) ||
+      (dtype == VSIG_DTYPE_F32 && !((float)vmax > (float)vmin && std::isfinite((float)vmax) &&
+                                    std::isfinite((float)vmin))))
+    return fail(c, VSIG_E_INVALID, "spectrogram image: need finite levels with vmax > vmin");
+  Timed t(c, "spectrogram_image");
+  HIPCHK(c, vsig::launch_spectrogram_image(dtype, sxx, n_freq, n_time, freq_fast != 0, ld, floor_, vmin,
+                                           vmax, median != 0, flip_freq != 0, pool_f, pool_t, lut_dev,
+                                           rgba_dev, c->stream));
+  return VSIG_OK;
+}
+
 }  // extern "C"

@@ -336,6 +336,15 @@ hipError_t launch_db_transform(int dtype, const void* a, long long n, double flo
 hipError_t launch_abs_c64(int dtype, const void* a, long long n, float2* out, hipStream_t st);
 hipError_t launch_abs_c128(int dtype, const void* a, long long n, double2* out, hipStream_t st);
 
+// display.hip: Sxx (n_freq x n_time, VSIG_F32 / VSIG_F64; frame-major memory
+// when freq_fast, else C-contiguous; ld elements between rows of the fast axis)
+// -> ceil(n_freq / pf) x ceil(n_time / pt) RGBA pixels through the 259-row
+// colour table lut (see the file's header).  lut and rgba are 4-byte aligned.
+hipError_t launch_spectrogram_image(int dtype, const void* sxx, long long n_freq, long long n_time,
+                                    int freq_fast, long long ld, double floor_, double vmin, double vmax,
+                                    int median, int flip, int pf, int pt, const unsigned char* lut,
+                                    unsigned char* rgba, hipStream_t st);
+
 // peaks.hip: the peak list of |a| (threshold + first maximum of a +-d window;
 // see the file's header).  thr: absolute, or with `relative` a ratio of
 // max |a| multiplied on the device.  out: the first `cap` instances in
