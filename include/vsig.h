@@ -247,7 +247,9 @@ int vsig_correlate_c64(vsig_ctx* ctx, const void* a, int64_t na, const void* v, 
 
 /* ---- transforms of any length (bigfft.hip: four-step FFT on the in-LDS engine
  * for powers of two above 16384, Bluestein / chirp-z for every other length,
- * up to 2^27 points; complex64 arithmetic).
+ * up to 2^27 points; complex64 arithmetic).  vsig_dft_dev, vsig_resample_dev and
+ * vsig_filter_channel_dev run a power of two from 256 to 16384 points as one
+ * in-LDS transform of that length.
  * vsig_dft_dev: batch frames of n contiguous samples, y[f][k] = sum_j x[f][j]
  *   e^{-+2 pi i jk/n} (inverse: + and 1/n, numpy.fft's convention).
  * vsig_resample_dev: scipy.signal.resample(x, num) as resample_signal calls it

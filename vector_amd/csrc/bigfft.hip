@@ -21,7 +21,10 @@
 // M <= 16384: one block per frame does all of it in LDS (bf_small_kernel);
 // larger: column pass (load x c) -> row pass (FFT, * B, IFFT, same block) ->
 // inverse column pass (store c X).  The chirps are formed in double on the
-// device from n^2 mod 2N (exact integers).
+// device from n^2 mod 2N (exact integers).  A power of two from 256 to 16384
+// points needs none of this: dft_any (vsig_api.hip) runs it as one transform
+// of its own plan (bf_small_kernel MODE 1, inverse by conj), half the error of
+// the chirp-z's three transforms (tests/test_gpu_accuracy.py).
 //
 // Used by resample_signal (utils.py:107-118: scipy.signal.resample = FFT of
 // any length, spectrum copy, inverse FFT of any length), the channel filter
