@@ -176,7 +176,8 @@ int vsig_clock_read(vsig_ctx* ctx, const char* kernel, double* ghz, int64_t* tic
 
 /* ---- spectrum: Sxx[f, k] = |sum_{i<nperseg} w[i] x[f*hop + i] e^{-2 pi j k i / nfft}|^2 * scale
  * nfft: any length >= nperseg up to 2^27 (powers of two in [64, 2^28]: in-LDS plans, above
- *   16384 a four-step FFT per frame; other lengths: Bluestein per frame, bigfft.hip);
+ *   16384 a four-step FFT per frame; other lengths: a direct sum in double up to 512 points,
+ *   Bluestein per frame beyond, bigfft.hip);
  * nframes = (n - nperseg) / hop + 1;
  * sxx is frame-major float32 [nframes][nfft] (Sxx of scipy is its transpose);
  * shift = 1 stores bin k at (k + nfft/2) % nfft (np.fft.fftshift).
@@ -245,11 +246,14 @@ int vsig_correlate_c64_dev(vsig_ctx* ctx, const void* a, int64_t na, const void*
 int vsig_correlate_c64(vsig_ctx* ctx, const void* a, int64_t na, const void* v, int64_t nv,
                        int32_t mode, void* c, vsig_peak_t* peak);
 
-/* ---- transforms of any length (bigfft.hip: four-step FFT on the in-LDS engine
- * for powers of two above 16384, Bluestein / chirp-z for every other length,
- * up to 2^27 points; complex64 arithmetic).  vsig_dft_dev, vsig_resample_dev and
- * vsig_filter_channel_dev run a power of two from 256 to 16384 points as one
- * in-LDS transform of that length.
+/* ---- transforms of any length (bigfft.hip; complex64 arithmetic).
+ * vsig_dft_dev, vsig_resample_dev and vsig_filter_channel_dev run a power of
+ * two from 256 to 16384 points as one in-LDS transform of that length, a power
+ * of two from 2^15 to 2^28 points as one four-step FFT of that length on the
+ * in-LDS engine, every other length up to 512 points (the powers of two below
+ * 256 included) as the sum itself in double precision, and every other length
+ * from 513 to 2^27 points as a Bluestein / chirp-z convolution of M >= 2n - 1
+ * points.
  * vsig_dft_dev: batch frames of n contiguous samples, y[f][k] = sum_j x[f][j]
  *   e^{-+2 pi i jk/n} (inverse: + and 1/n, numpy.fft's convention).
  * vsig_resample_dev: scipy.signal.resample(x, num) as resample_signal calls it

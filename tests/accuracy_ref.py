@@ -38,6 +38,20 @@ the references differ in arithmetic only, never in input.
                   inter-pass twiddles off by uniform +-ulp spacings (or formed
                   as TwLds forms them)
   spectrum_input  the seeded input of a spectrum case (SPECTRUM_SEEDS)
+
+and for the routes of test_gpu_accuracy_routes.py:
+
+  resample        scipy.signal.resample's spectrum copy around scipy.fft
+  filter_channel  oracle.ref.filter_channel around scipy.fft
+  filter_channel_exact  the same masked inverse sum evaluated directly in
+                  np.longdouble at chosen output samples
+  chirpz          the three-transform chirp-z composite of an M-point engine
+  mix             apply_frequency_shift at a global sample offset (numpy's phase
+                  order, or the fused FIR loads' own)
+  mix_rot_model   numpy model of the fused mixer's rotation (vsig_kernels.h)
+  correlate       np.correlate(a, v, mode) by one FFT of the whole length
+  model_fourstep  the fp32 model of bigfft.hip's two-pass transform
+  floor / say     the bound itself and its ``ACC`` line
 """
 import numpy as np
 import scipy.fft
@@ -288,3 +302,337 @@ def spectrum_premise(x, nperseg, noverlap, nfft, ulp):
     e_ref = rel_rms(r32, r64)
     frame = max(rel_rms(y[:, f], r64[:, f]) for f in range(y.shape[1]))
     return rel_rms(y, r64) / e_ref, max_norm(y, r64) / max_norm(r32, r64), frame / e_ref
+
+
+# ---------------------------------------------------------------------------
+# the bound (shared by test_gpu_accuracy.py and test_gpu_accuracy_routes.py)
+# ---------------------------------------------------------------------------
+def say(case, **figs):
+    print("ACC " + case + " " + " ".join(f"{k}={v:.4g}" for k, v in figs.items()))
+
+
+def floor(case, y, r32, r64, K, frame_axis=None):
+    """The bound: rel_rms over the case and of each frame, max-norm over the
+    case, each within K times the complex64 reference's own."""
+    e_ref, e_gpu = rel_rms(r32, r64), rel_rms(y, r64)
+    m_ref, m_gpu = max_norm(r32, r64), max_norm(y, r64)
+    figs = dict(e_ref=e_ref, e_gpu=e_gpu, ratio=e_gpu / e_ref, m_ref=m_ref, m_gpu=m_gpu,
+                m_ratio=m_gpu / m_ref)
+    e_frame = 0.0
+    if frame_axis is not None:
+        e_frame = max(rel_rms(np.take(y, f, axis=frame_axis), np.take(r64, f, axis=frame_axis))
+                      for f in range(y.shape[frame_axis]))
+        figs["frame_ratio"] = e_frame / e_ref
+    say(case, **figs)
+    assert e_gpu <= K * e_ref, (case, figs)
+    assert m_gpu <= K * m_ref, (case, figs)
+    assert e_frame <= K * e_ref, (case, figs)
+
+
+# ---------------------------------------------------------------------------
+# the two-pass (four-step) transform of bigfft.hip
+# ---------------------------------------------------------------------------
+def bigfft_split(M):
+    """(N1, N2) of bigfft.hip's bigfft_split."""
+    if M <= 16384:
+        return 1, M
+    n2 = min(max(M // 64, 512), 16384)
+    return M // n2, n2
+
+
+def model_fourstep(x):
+    """bf_col_kernel then bf_row_kernel in complex64: FFT_N1 down the columns of
+    x[n1 N2 + n2], times W_M^(n2 k1) formed as tw_big forms it (an fp32 product
+    of two tables rounded from double, S = ceil(log2 M / 2)), FFT_N2 along the
+    rows, X[k1 + N1 k2]."""
+    a = np.asarray(x).astype(np.complex64)
+    M = len(a)
+    N1, N2 = bigfft_split(M)
+    if N1 == 1:
+        return model_fft(a)
+    S = (int(np.log2(M)) + 1) // 2
+    hi = np.exp(-2j * np.pi * (np.arange(M >> S) << S) / M).astype(np.complex64)
+    lo = np.exp(-2j * np.pi * np.arange(1 << S) / M).astype(np.complex64)
+    A = a.reshape(N1, N2)
+    cols = np.stack([model_fft(A[:, n2]) for n2 in range(N2)], axis=1)       # [k1, n2]
+    m = np.arange(N1)[:, None] * np.arange(N2)[None, :]
+    cols = cols * (hi[m >> S] * lo[m & ((1 << S) - 1)])
+    assert cols.dtype == np.complex64
+    rows = np.stack([model_fft(cols[k1]) for k1 in range(N1)])               # [k1, k2]
+    return np.ascontiguousarray(rows.T).reshape(M)                            # k1 + N1 k2
+
+
+# seeds of the long / strided spectrum cases, chosen as SPECTRUM_SEEDS' are: the
+# first seed, counting up from nfft + nperseg + noverlap + stride, on which the
+# model of the case's route (model_fourstep above 16384 points: exact class;
+# the +-10 ulp model at 8192) stays within the multiple its K derives from.
+ROUTE_SPECTRUM_SEEDS = {                # (nfft, nperseg, noverlap, stride): seed   seeds tried
+    (32768, 32768, 0, 1): 65537,        # 1
+    (65536, 40000, 30000, 1): 135569,   # 33 (zero-filled, overlapping frames: the model's worst
+                                        #     frame sat at 1.6 .. 5.3 x on the seeds before)
+    (8192, 8192, 0, 2): 16386,          # 1
+    (8192, 8192, 0, 3): 16387,          # 1
+    (32768, 32768, 0, 2): 65539,        # 2
+    (32768, 32768, 0, 3): 65540,        # 2
+}
+
+
+def route_spectrum_class(nfft):
+    """(K, transform of one padded frame, the model's multiple) of a spectrum
+    case of test_gpu_accuracy_routes.py."""
+    if nfft > 16384:
+        return K_EXACT, model_fourstep, MODEL_EXACT
+    K, ulp, limit = spectrum_class(nfft)
+    return K, (lambda f: model_fft(f, ulp=ulp)), limit
+
+
+def route_spectrum_input(nfft, nperseg, noverlap, stride=1, seed=None):
+    """3 frames of synth_iq (taken every `stride` samples) under the case's seed."""
+    from oracle import ref
+    seed = ROUTE_SPECTRUM_SEEDS[nfft, nperseg, noverlap, stride] if seed is None else seed
+    return ref.synth_iq(stride * (nperseg + 2 * (nperseg - noverlap)), seed=seed)
+
+
+def route_spectrum_premise(x, nperseg, noverlap, nfft, stride=1):
+    """spectrum_premise with the route's model, on x[::stride]."""
+    xs = np.asarray(x)[::stride]
+    model = route_spectrum_class(nfft)[1]
+    r64 = spectrum(xs, "hann", nperseg, noverlap, nfft, np.complex128)
+    r32 = spectrum(xs, "hann", nperseg, noverlap, nfft)
+    y = spectrum(xs, "hann", nperseg, noverlap, nfft, transform=model)
+    e_ref = rel_rms(r32, r64)
+    frame = max(rel_rms(y[:, f], r64[:, f]) for f in range(y.shape[1]))
+    return rel_rms(y, r64) / e_ref, max_norm(y, r64) / max_norm(r32, r64), frame / e_ref
+
+
+# ---------------------------------------------------------------------------
+# resample_signal, filter_channel, chirp-z
+# ---------------------------------------------------------------------------
+def resample(x, num, dtype=np.complex64, real_input=False):
+    """scipy.signal.resample(x, num) (scipy 1.15.3, domain='time', no window)
+    restated around scipy.fft with the dtype kept, as oracle.ref.resample_signal
+    restates it: the complex path, the imaginary part zeroed for real input."""
+    x = np.asarray(x)
+    real = _real_of(dtype)
+    Nx, num = len(x), int(num)
+    X = _kept(scipy.fft.fft(x.astype(dtype)), dtype)
+    Y = np.zeros(num, dtype)
+    N = min(num, Nx)
+    nyq = N // 2 + 1
+    Y[:nyq] = X[:nyq]
+    if N > 2:
+        Y[nyq - N:] = X[nyq - N:]
+    if N % 2 == 0:
+        if num < Nx:
+            Y[-N // 2] += X[-N // 2]
+        elif Nx < num:
+            Y[N // 2] *= real(0.5)
+            Y[num - N // 2] = Y[N // 2]
+    y = _kept(scipy.fft.ifft(Y), dtype) * real(float(num) / float(Nx))
+    if real_input:
+        y = y.real.astype(dtype)
+    return _kept(y, dtype)
+
+
+CENTER_FREQ = 5230e6
+
+
+def channel_mask(n, center_freq, sample_rate, bandwidth):
+    """oracle.ref.filter_channel's brick-wall mask over the n bins (its axis
+    with the extra * sample_rate)."""
+    freqs = np.fft.fftfreq(n, 1 / sample_rate) * sample_rate + CENTER_FREQ
+    return (freqs >= center_freq - bandwidth / 2) & (freqs <= center_freq + bandwidth / 2)
+
+
+def filter_channel(x, center_freq, sample_rate, bandwidth, dtype=np.complex64):
+    """oracle.ref.filter_channel around scipy.fft with the dtype kept: the real
+    dtype's array of len(x)."""
+    x = np.asarray(x)
+    n = len(x)
+    freqs = np.fft.fftfreq(n, 1 / sample_rate) * sample_rate + CENTER_FREQ
+    X = _kept(scipy.fft.fft(x.astype(dtype)), dtype)
+    mask = channel_mask(n, center_freq, sample_rate, bandwidth)
+    F = np.zeros(n, dtype)
+    F[mask] = X[mask]
+    neg = np.fft.fftshift(freqs) < CENTER_FREQ
+    pos = np.fft.fftshift(freqs) >= CENTER_FREQ
+    Fs = np.fft.fftshift(F)
+    Fs[neg] = np.conj(np.flip(Fs[pos]))
+    y = _kept(scipy.fft.ifft(np.fft.ifftshift(Fs)), dtype).real
+    assert y.dtype == _real_of(dtype)
+    return y
+
+
+def _ld_table(n):
+    """exp(-2 pi i r / n), r < n, as np.longdouble (cos, sin)."""
+    ld = np.longdouble
+    a = (2 * (4 * np.arctan(ld(1)))) * np.arange(n, dtype=ld) / ld(n)
+    return np.cos(a), -np.sin(a)
+
+
+def filter_channel_exact(x, center_freq, sample_rate, bandwidth, samples):
+    """The channel filter's masked inverse sum evaluated directly in
+    np.longdouble at the output indices `samples` (even n):
+        X[k] = sum_m x[m] e^{-2 pi i k m / n}         for the kept bins k < n/2,
+        y[m] = Re sum_k (X[k] e^{2 pi i k m / n} + conj X[k] e^{2 pi i (n-1-k) m / n}) / n
+    (the mirror of bin k lands on bin n - 1 - k).  Phases from k m mod n."""
+    ld = np.longdouble
+    x = np.asarray(x)
+    n = len(x)
+    keep = np.flatnonzero(channel_mask(n, center_freq, sample_rate, bandwidth)[:n // 2])
+    samples = np.asarray(samples, np.int64)
+    if len(keep) == 0:
+        return np.zeros(len(samples), ld)
+    tc, ts = _ld_table(n)                       # e^{-i a}: (cos a, -sin a)
+    xr, xi = x.real.astype(ld), x.imag.astype(ld)
+    m = np.arange(n, dtype=np.int64)
+    Xr, Xi = np.empty(len(keep), ld), np.empty(len(keep), ld)
+    for j0 in range(0, len(keep), 64):
+        r = (keep[j0:j0 + 64, None] * m[None, :]) % n
+        c, s = tc[r], ts[r]
+        Xr[j0:j0 + 64] = (xr * c - xi * s).sum(axis=1)
+        Xi[j0:j0 + 64] = (xr * s + xi * c).sum(axis=1)
+    y = np.empty(len(samples), ld)
+    for i0 in range(0, len(samples), 64):
+        mm = samples[i0:i0 + 64, None]
+        r1 = (keep[None, :] * mm) % n
+        r2 = ((n - 1 - keep)[None, :] * mm) % n
+        # e^{+i a} = (tc, -ts)
+        t = Xr * tc[r1] + Xi * ts[r1] + Xr * tc[r2] - Xi * ts[r2]
+        y[i0:i0 + 64] = t.sum(axis=1) / ld(n)
+    return y
+
+
+CHANNEL_DIRECT = dict(n=20_000, cf=5230e6 + 100.0, sr=4000.0, bw=2e6)
+_channel_direct = []
+
+
+def channel_direct_refs():
+    """The direct-route case of filter_channel (bins 800 Hz apart on the
+    reference's axis: 1251 kept bins of 20 000 samples): x, the 512 output samples checked (2.56 % of the length: evenly
+    spread, plus both ends' neighbours), the np.longdouble evaluation L there,
+    and d = max_norm of numpy's own double-precision FFT route
+    (oracle.ref.filter_channel) against L.  Computed once."""
+    from oracle import ref
+    if not _channel_direct:
+        p = CHANNEL_DIRECT
+        x = ref.synth_iq(p["n"], seed=46)
+        idx = np.unique(np.concatenate([np.linspace(0, p["n"] - 1, 510).astype(np.int64), [1, p["n"] - 2]]))
+        L = filter_channel_exact(x, p["cf"], p["sr"], p["bw"], idx)
+        # complex128 in: numpy's FFT runs in the precision of its input
+        want = ref.filter_channel(x.astype(np.complex128), p["cf"], p["sr"], p["bw"])[idx]
+        d = float(np.abs(want.astype(np.longdouble) - L).max() / np.abs(L).max())
+        _channel_direct.append((x, idx, L, d))
+    return _channel_direct[0]
+
+
+def chirpz(x, M, inverse=False, dtype=np.complex64, transform=None):
+    """The DFT of len(x) points as bigfft.hip's Bluestein route forms it, with
+    scipy.fft as the M-point engine: a = x c zero-padded, X = c IFFT_M(FFT_M(a)
+    FFT_M(b)), c[n] = exp(-i pi n^2 / N) from n^2 mod 2N, rounded to the dtype.
+    A composite reference for a composite route.  transform: a stand-in for
+    the forward M-point transform (the engine's model; complex64, the inverse by
+    conj and B = FFT_M(b / M) as the kernels form them)."""
+    x = np.asarray(x).astype(dtype)
+    N = len(x)
+    assert M >= 2 * N - 1
+    k = np.arange(N, dtype=np.int64)
+    c = np.exp(-1j * np.pi * ((k * k) % (2 * N)) / N).astype(dtype)
+    if inverse:
+        x = np.conj(x)
+    a = np.zeros(M, dtype)
+    a[:N] = x * c
+    b = np.zeros(M, dtype)
+    b[:N] = np.conj(c)
+    b[M - N + 1:] = np.conj(c[1:][::-1])
+    if transform is None:
+        A = _kept(scipy.fft.fft(a), dtype)
+        B = _kept(scipy.fft.fft(b), dtype)
+        conv = _kept(scipy.fft.ifft(A * B), dtype)
+    else:
+        B = transform(b * _real_of(dtype)(1.0 / M))
+        conv = _kept(np.conj(transform(np.conj(transform(a) * B))), dtype)
+    y = (c * conv[:N]).astype(dtype)
+    if inverse:
+        y = np.conj(y) * _real_of(dtype)(1.0 / N)
+    return _kept(y, dtype)
+
+
+def chirpz_size(N):
+    """M of dft_any's Bluestein plan: the power of two >= max(256, 2N - 1)."""
+    M = 256
+    while M < 2 * N - 1:
+        M *= 2
+    return M
+
+
+# ---------------------------------------------------------------------------
+# the mixers
+# ---------------------------------------------------------------------------
+def mix_phase(n, f, sr, i0, order="numpy"):
+    """theta of apply_frequency_shift at global samples i0 .. i0 + n - 1 in
+    float64.  order="numpy": w = 2 pi f, t = (i0 + arange(n)) / sr, w * t (the
+    standalone mixer's order); order="fused": (w / sr) * gi, the fused FIR
+    loads' order (vsig_kernels.h: mix_rot_fast)."""
+    w = 2 * np.pi * f
+    gi = (int(i0) + np.arange(n, dtype=np.int64)).astype(np.float64)
+    assert int(i0) + n < 2 ** 53
+    if order == "numpy":
+        return w * (gi / sr)
+    assert order == "fused"
+    return (w / sr) * gi
+
+
+def mix(x, f, sr, i0=0, dtype=np.complex64, order="numpy"):
+    """x * exp(1j * theta) in complex128, rounded to complex64 for dtype
+    complex64 (oracle.ref.apply_frequency_shift with a sample offset)."""
+    x = np.asarray(x)
+    y = x.astype(np.complex128) * np.exp(1j * mix_phase(len(x), f, sr, i0, order))
+    return _kept(y.astype(dtype), dtype)
+
+
+def mix_rot_model(n, f, sr, i0):
+    """numpy model of mix_rot_fast / cis_rev (vsig_kernels.h): the phase in
+    revolutions ((w / sr) / 2 pi) * gi in float64, reduced to a quarter turn and
+    |g| <= 1/8 turn in float64, fp32 Taylor polynomials of degree 9 / 10."""
+    f32 = np.float32
+    wsr = (2 * np.pi * f) / sr
+    gi = (int(i0) + np.arange(n, dtype=np.int64)).astype(np.float64)
+    rev = (wsr * 1.59154943091895345608e-01) * gi
+    fr = rev - np.rint(rev)
+    q = np.rint(4.0 * fr)
+    x = (fr - 0.25 * q).astype(f32) * f32(6.283185307179586)
+    x2 = x * x
+    sn = x * ((((x2 * f32(2.7557319e-6) + f32(-1.9841270e-4)) * x2 + f32(8.3333333e-3)) * x2
+               + f32(-1.6666667e-1)) * x2 + f32(1.0))
+    cs = ((((x2 * f32(-2.7557319e-7) + f32(2.4801587e-5)) * x2 + f32(-1.3888889e-3)) * x2
+           + f32(4.1666667e-2)) * x2 + f32(-0.5)) * x2 + f32(1.0)
+    assert sn.dtype == cs.dtype == np.float32
+    qi = q.astype(np.int64) & 3
+    c = np.choose(qi, [cs, -sn, -cs, sn])
+    s = np.choose(qi, [sn, cs, -sn, -cs])
+    return (c + 1j * s).astype(np.complex64)
+
+
+# ---------------------------------------------------------------------------
+# np.correlate in every mode
+# ---------------------------------------------------------------------------
+def correlate(a, v, mode="full", dtype=np.complex64):
+    """np.correlate(a, v, mode): c[l] = sum_n a[n + l] conj(v[n]) over the lags
+    -(len(v) - 1) .. len(a) - 1 ('full'), by one FFT of the whole length; 'same'
+    and 'valid' are numpy's slices of it."""
+    a, v = np.asarray(a), np.asarray(v)
+    na, nv = len(a), len(v)
+    L = scipy.fft.next_fast_len(na + nv - 1)
+    A = scipy.fft.fft(a.astype(dtype), L)
+    V = scipy.fft.fft(v.astype(dtype), L)
+    c = _kept(scipy.fft.ifft(A * np.conj(V)), dtype)
+    full = np.concatenate([c[L - (nv - 1):], c[:na]]) if nv > 1 else c[:na]
+    lo, hi = min(na, nv), max(na, nv)
+    if mode == "full":
+        return full
+    if mode == "valid":
+        return full[lo - 1:hi]
+    assert mode == "same"
+    start = (lo - 1) // 2 if na >= nv else lo - 1 - (lo - 1) // 2
+    return full[start:start + hi]

@@ -169,6 +169,164 @@ def test_pfb_references(C, P, cut):
     assert r32.dtype == np.complex64 and 1e-8 < acc.rel_rms(r32, r64) < 5e-7
 
 
+# ---------------------------------------------------------------------------
+# the references of test_gpu_accuracy_routes.py
+# ---------------------------------------------------------------------------
+def test_floor_rejects_and_accepts():
+    r64 = np.fft.fft(acc.noise(256, 1).astype(np.complex128))
+    r32 = acc.dft(acc.noise(256, 1))
+    acc.floor("self", r32, r32, r64, 1.0)
+    with pytest.raises(AssertionError):
+        acc.floor("worse", r64 + 4 * (r32 - r64), r32, r64, acc.K_EXACT)
+
+
+@pytest.mark.parametrize("M", [1 << 15, 1 << 16])
+def test_fourstep_model_is_exact_class(M):
+    """bigfft.hip's two passes with tw_big's one extra product: within the
+    multiple K_EXACT was derived from, on noise."""
+    assert acc.bigfft_split(M) == (64, M // 64)
+    assert acc.bigfft_split(1 << 21) == (128, 16384) and acc.bigfft_split(16384) == (1, 16384)
+    x = acc.noise(M, seed=M)
+    r = np.fft.fft(x.astype(np.complex128))
+    s, y = acc.dft(x), acc.model_fourstep(x)
+    assert y.dtype == np.complex64
+    got = acc.rel_rms(y, r) / acc.rel_rms(s, r), acc.max_norm(y, r) / acc.max_norm(s, r)
+    print(M, "four-step model multiples (rms, max): %.2f %.2f" % got)
+    assert max(got) <= acc.MODEL_EXACT
+
+
+@pytest.mark.parametrize("case", sorted(acc.ROUTE_SPECTRUM_SEEDS))
+def test_route_spectrum_inputs_meet_the_derivation(case):
+    """The seed table of the long and strided spectrum cases, as
+    test_spectrum_inputs_meet_the_derivation pins SPECTRUM_SEEDS."""
+    nfft, nperseg, noverlap, stride = case
+    limit = acc.route_spectrum_class(nfft)[2]
+    x = acc.route_spectrum_input(nfft, nperseg, noverlap, stride)
+    assert len(x) == stride * (nperseg + 2 * (nperseg - noverlap))
+    got = acc.route_spectrum_premise(x, nperseg, noverlap, nfft, stride)
+    print(case, "model multiples (rms, max, frame): %.2f %.2f %.2f" % got)
+    assert max(got) <= limit
+
+
+@pytest.mark.parametrize("n,num", [(4096, 2048), (5000, 2500), (5000, 14_000), (3001, 1234), (1234, 3001)])
+def test_resample_references(n, num):
+    x = ref.synth_iq(n, seed=n + num)
+    a, b = float(n), float(num)
+    want = ref.resample_signal(x.astype(np.complex128), a, b)          # rounded to complex64
+    assert want.shape == (num,)
+    r64 = acc.resample(x, num, np.complex128)
+    np.testing.assert_array_equal(r64.astype(np.complex64), want)
+    r32 = acc.resample(x, num)
+    assert r32.dtype == np.complex64 and 1e-8 < acc.rel_rms(r32, r64) < 5e-7
+    xr = np.cos(0.01 * np.arange(n)).astype(np.float32)
+    wr = ref.resample_signal(xr.astype(np.float64), a, b)
+    rr = acc.resample(xr, num, np.complex128, real_input=True)
+    assert np.all(rr.imag == 0)
+    np.testing.assert_array_equal(rr.astype(np.complex64), wr)
+
+
+@pytest.mark.parametrize("n,cf,sr,bw", [(2000, 5230e6 + 100.0, 800.0, 2e6), (4096, 5230e6, 56e6, 60e6),
+                                        (4094, 5230e6, 70.0, 3000.0), (1000, 5230e6 + 40.0, 100.0, 50.0)])
+def test_filter_channel_references(n, cf, sr, bw):
+    x = ref.synth_iq(n, seed=n)
+    want = ref.filter_channel(x.astype(np.complex128), cf, sr, bw)
+    r64 = acc.filter_channel(x, cf, sr, bw, np.complex128)
+    assert r64.dtype == np.float64 and acc.max_norm(r64, want) < 1e-13
+    r32 = acc.filter_channel(x, cf, sr, bw)
+    assert r32.dtype == np.float32 and 1e-8 < acc.rel_rms(r32, r64) < 5e-7
+    # the direct np.longdouble evaluation computes the same function
+    idx = np.unique(np.linspace(0, n - 1, 64).astype(np.int64))
+    L = acc.filter_channel_exact(x, cf, sr, bw, idx)
+    assert L.dtype == np.longdouble
+    assert np.abs(L - want[idx]).max() <= 1e-13 * np.abs(want).max()
+
+
+def test_filter_channel_double_fft_error():
+    """d of test_gpu_accuracy_routes.test_filter_channel_direct_route: numpy's
+    double-precision FFT route against the np.longdouble sum, at 512 of the
+    20 000 output samples (2.56 %)."""
+    x, idx, L, d = acc.channel_direct_refs()
+    print("filter_channel n=20000: d = %.3g at %d samples" % (d, len(idx)))
+    assert len(idx) == 512 and 1e-17 < d < 1e-14
+    assert np.finfo(np.longdouble).eps < 1e-18        # an 80-bit L resolves d
+
+
+@pytest.mark.parametrize("n,M", [(255, 512), (1000, 2048), (5000, 16384)])
+def test_chirpz_reference(n, M):
+    assert acc.chirpz_size(n) == M
+    x = ref.synth_iq(n, seed=n)
+    for inv in (False, True):
+        r64 = acc.dft(x, inv, np.complex128)
+        assert acc.max_norm(acc.chirpz(x, M, inv, np.complex128), r64) < 1e-12
+        c32 = acc.chirpz(x, M, inv)
+        assert c32.dtype == np.complex64 and 5e-8 < acc.rel_rms(c32, r64) < 1e-6
+
+
+def test_chirpz_model_at_257_points():
+    """Why dft_any sums short lengths directly: as a chirp-z (M = 1024) 257 points
+    missed K_EXACT in max-norm on the GPU (2.19e-7, 3.5 x scipy's).  The chirp-z
+    with the engine's exact-twiddle model as its 1024-point transform lands on
+    the same figure without a GPU: its rel_rms is 1.1 x scipy's, but the
+    engine's error in a dominant bin, taken three times, is 3.5 x scipy's there
+    (scipy's own max-norm error on synth_iq(257, seed=257) is 0.29 of its
+    rel_rms).  Over twelve seeds the model's max-norm multiple ranges from 1.0
+    to 3.8."""
+    n, M = 257, 1024
+    x = ref.synth_iq(n, seed=n)
+    r64, r32 = acc.dft(x, False, np.complex128), acc.dft(x)
+    y = acc.chirpz(x, M, transform=acc.model_fft)
+    assert y.dtype == np.complex64
+    rms, mx = acc.rel_rms(y, r64) / acc.rel_rms(r32, r64), acc.max_norm(y, r64) / acc.max_norm(r32, r64)
+    print("chirp-z model n=257: %.2f x scipy rel_rms, %.2f x scipy max-norm (%.3g)" % (rms, mx, acc.max_norm(y, r64)))
+    assert rms <= acc.MODEL_EXACT
+    assert 3.0 < mx < 4.0
+    assert acc.max_norm(r32, r64) < 0.35 * acc.rel_rms(r32, r64)
+
+
+MIX_OFFSETS = [0, (1 << 31) - 2048, (1 << 32) - 2048, (1 << 34) + 12_345]
+MIX_TONES = [(1.5e6, 56e6), (-13.37e6, 56e6), (0.31, 1.0)]
+
+
+def test_mix_reference_is_the_oracle():
+    x = ref.synth_iq(5000, seed=3)
+    for f, sr in MIX_TONES:
+        np.testing.assert_array_equal(acc.mix(x, f, sr), ref.apply_frequency_shift(x, f, sr))
+        assert acc.mix(x, f, sr, 12345, np.complex128).dtype == np.complex128
+    # exact against rational arithmetic where the phase is a rational turn
+    r = acc.mix(np.ones(8, np.complex64), 0.25, 1.0, (1 << 34), np.complex128)
+    np.testing.assert_allclose(r, 1j ** np.arange(8), atol=1e-5)      # theta ~ 2.7e10: spacing 3.8e-6
+
+
+@pytest.mark.parametrize("f,sr", MIX_TONES)
+@pytest.mark.parametrize("i0", MIX_OFFSETS)
+def test_fused_mixer_phase_model(i0, f, sr):
+    """The fused loads' rotation (cis_rev on ((w / sr) / 2 pi) * gi) against
+    numpy's phase order: within 1e-6 + 4 spacings of theta per sample, the
+    bound test_fused_mixer_phase holds the kernel to; and the 'fused' order of
+    acc.mix is that rotation to fp32 accuracy."""
+    n = 3 * 1024 + 77 + 254
+    th = acc.mix_phase(n, f, sr, i0)
+    sp = float(np.spacing(np.abs(th).max()))
+    y = acc.mix_rot_model(n, f, sr, i0).astype(np.complex128)
+    e = np.abs(y - np.exp(1j * th)).max()
+    e_fused = np.abs(y - np.exp(1j * acc.mix_phase(n, f, sr, i0, "fused"))).max()
+    print(f"i0={i0} f={f:g} sr={sr:g}: model - numpy order {e:.3g} = {(e - 7e-8) / sp:.2f} spacings "
+          f"+ 7e-8; model - fused order {e_fused:.3g}; spacing {sp:.3g}")
+    assert e <= 1e-6 + 4 * sp
+    assert e <= 1e-7 + 2.5 * sp                       # with room: the fp32 polynomial plus ~2 spacings
+    assert e_fused <= 1e-7 + 1.5 * sp
+
+
+@pytest.mark.parametrize("na,nv", [(300, 40), (40, 300), (41, 300), (300, 41), (64, 64), (1, 7)])
+@pytest.mark.parametrize("mode", ["full", "same", "valid"])
+def test_correlate_reference_modes(na, nv, mode):
+    a, v = ref.synth_iq(na, seed=na), ref.synth_iq(nv, seed=nv + 1)
+    want = np.correlate(a.astype(np.complex128), v.astype(np.complex128), mode)
+    r64 = acc.correlate(a, v, mode, np.complex128)
+    assert r64.shape == want.shape and acc.max_norm(r64, want) < 1e-13
+    assert acc.correlate(a, v, mode).dtype == np.complex64
+
+
 @pytest.mark.parametrize("n", [1000, 12_289])
 def test_dft_references(n):
     x = ref.synth_iq(n, seed=n)

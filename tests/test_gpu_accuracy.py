@@ -64,26 +64,7 @@ def _k_spectrum(nfft):
     return acc.spectrum_class(nfft)[0]
 
 
-def _say(case, **figs):
-    print("ACC " + case + " " + " ".join(f"{k}={v:.4g}" for k, v in figs.items()))
-
-
-def _floor(case, y, r32, r64, K, frame_axis=None):
-    """The section's bound: rel_rms over the case and of each frame, max-norm
-    over the case."""
-    e_ref, e_gpu = acc.rel_rms(r32, r64), acc.rel_rms(y, r64)
-    m_ref, m_gpu = acc.max_norm(r32, r64), acc.max_norm(y, r64)
-    figs = dict(e_ref=e_ref, e_gpu=e_gpu, ratio=e_gpu / e_ref, m_ref=m_ref, m_gpu=m_gpu,
-                m_ratio=m_gpu / m_ref)
-    e_frame = 0.0
-    if frame_axis is not None:
-        e_frame = max(acc.rel_rms(np.take(y, f, axis=frame_axis), np.take(r64, f, axis=frame_axis))
-                      for f in range(y.shape[frame_axis]))
-        figs["frame_ratio"] = e_frame / e_ref
-    _say(case, **figs)
-    assert e_gpu <= K * e_ref, (case, figs)
-    assert m_gpu <= K * m_ref, (case, figs)
-    assert e_frame <= K * e_ref, (case, figs)
+_say, _floor = acc.say, acc.floor      # the bound and its ACC line (accuracy_ref.py)
 
 
 # ---------------------------------------------------------------------------

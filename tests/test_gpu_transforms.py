@@ -1,5 +1,6 @@
-"""Transforms of any length (bigfft.hip: four-step FFT above 16384 points,
-Bluestein for every other length) and the reference functions built on them:
+"""Transforms of any length (bigfft.hip: four-step FFT above 16384 points, a
+direct sum up to 512, Bluestein for every other length) and the reference
+functions built on them:
 
 * resample_signal (utils.py:107-118, scipy.signal.resample) against
   tests/golden/stream_ops.npz (made by the reference);

@@ -6,12 +6,15 @@
 //                 times W_M^(n2 k1)        (strided loads / stores, F adjacent
 //                 columns per block so a wave's lanes read F-sample runs);
 //   row pass    : X[k1 + N1 k2] = FFT_N2 over n2 of X1[k1, n2] (contiguous rows);
-// the spectrum stays in that permuted order (element k1 N2 + k2 holds
-// X[k1 + N1 k2]) because every consumer here is element-wise: the PSD of long
-// frames stores |X|^2 at its natural index, and Bluestein's convolution
-// multiplies by a kernel spectrum kept in the same order and runs the inverse
-// passes back (row inverse, conj twiddles, inverse column pass) to natural
-// order.  Inverse transforms by conj: IFFT(v) = conj(FFT(conj(v))).
+// inside a convolution the spectrum stays in that permuted order (element
+// k1 N2 + k2 holds X[k1 + N1 k2]): Bluestein multiplies by a kernel spectrum
+// kept in the same order and runs the inverse passes back (row inverse, conj
+// twiddles, inverse column pass) to natural order.  A consumer of the spectrum
+// itself gets it at its natural index from the row pass's store: |X|^2 for the
+// PSD of long frames (MODE 2), X through a BfOut for the DFT of a power of two
+// from 2^15 to 2^28 points (MODE 3: dft_any in vsig_api.hip runs those as this
+// one transform of N points, not as a chirp-z).  Inverse transforms by conj:
+// IFFT(v) = conj(FFT(conj(v))).
 //
 // Bluestein (chirp-z) for any length N: with c[n] = exp(-i pi n^2 / N),
 //   X[k] = c[k] sum_n (x[n] c[n]) conj(c[k - n]),
@@ -21,10 +24,14 @@
 // M <= 16384: one block per frame does all of it in LDS (bf_small_kernel);
 // larger: column pass (load x c) -> row pass (FFT, * B, IFFT, same block) ->
 // inverse column pass (store c X).  The chirps are formed in double on the
-// device from n^2 mod 2N (exact integers).  A power of two from 256 to 16384
-// points needs none of this: dft_any (vsig_api.hip) runs it as one transform
-// of its own plan (bf_small_kernel MODE 1, inverse by conj), half the error of
-// the chirp-z's three transforms (tests/test_gpu_accuracy.py).
+// device from n^2 mod 2N (exact integers).  A power of two from 256 points up
+// needs none of this: dft_any (vsig_api.hip) runs it as one transform, of its
+// own plan up to 16384 points (bf_small_kernel MODE 1, inverse by conj) and
+// four-step from 2^15 to 2^28, a half to a sixth of the max-norm error of the
+// chirp-z's three transforms (tests/test_gpu_accuracy.py,
+// tests/test_gpu_accuracy_routes.py).  Every other length up to 512 points --
+// the powers of two below 256 included -- is summed directly in double
+// (bf_direct_kernel); from 513 points to N = 2^27 (M <= 2^28) it is a chirp-z.
 //
 // Used by resample_signal (utils.py:107-118: scipy.signal.resample = FFT of
 // any length, spectrum copy, inverse FFT of any length), the channel filter
@@ -161,11 +168,13 @@ constexpr int row_frames() {
 // MODE 0 (Bluestein): FFT_N2, * Bk[k1 N2 + k2], IFFT_N2 (conj trick), back to tmp.
 // MODE 1 (kernel spectrum): FFT_N2 * scale back to tmp (permuted order).
 // MODE 2 (PSD): |X|^2 * scale into psd[f][shift(k)], k = k1 + N1 k2 (float32).
-// MODE 3: X * scale at its natural index into ((float2*) psd)[f][k].
+// MODE 3: X at its natural index k = k1 + N1 k2 through out (BfOut: conj, scale,
+//         complex64 / complex128 / real part) -- the second pass of a plain
+//         four-step DFT.
 template <class P, int MODE>
 __global__ __launch_bounds__(row_frames<P>() * P::TF) void bf_row_kernel(
     float2* __restrict__ tmp, int N1, long long M, const float2* __restrict__ Bk,
-    const float2* __restrict__ tw, float scale, float* __restrict__ psd, int shift) {
+    const float2* __restrict__ tw, float scale, float* __restrict__ psd, int shift, BfOut out) {
   static_assert(P::R[0] == P::RL, "in-register convolution needs a palindromic plan");
   constexpr int F = row_frames<P>();
   constexpr int N2 = P::N;
@@ -199,10 +208,8 @@ __global__ __launch_bounds__(row_frames<P>() * P::TF) void bf_row_kernel(
       of[o] = (v[e].x * v[e].x + v[e].y * v[e].y) * scale;
     }
   } else {
-    float2* of = reinterpret_cast<float2*>(psd) + f * M;
 #pragma unroll
-    for (int e = 0; e < P::E; ++e)
-      of[k1 + (long long)N1 * out_index<P>(t, e)] = make_float2(v[e].x * scale, v[e].y * scale);
+    for (int e = 0; e < P::E; ++e) out(f, k1 + (long long)N1 * out_index<P>(t, e), v[e]);
   }
 }
 
@@ -230,6 +237,48 @@ __global__ __launch_bounds__(P::TF) void bf_small_kernel(BfIn in, BfOut out,
   } else {
 #pragma unroll
     for (int e = 0; e < P::E; ++e) out(f, out_index<P>(t, e), v[e]);
+  }
+}
+
+// Short frames without a plan (N <= kDirectMax = 512): X[k] = sum_n x[n] W_N^(nk)
+// summed directly in double, one frame per block.  W_N^m comes from sincospi
+// in double (exact at the multiples of a quarter turn), the index n k mod N is
+// stepped by additions, and the one rounding to fp32 is the store's: at these
+// lengths a chirp-z costs three transforms of 2N .. 4N points plus two chirp
+// products, and the engine's error in a dominant bin, taken three times, missed
+// the bound of tests/test_gpu_accuracy_routes.py at 257 points (3.5 x complex64
+// scipy's max-norm error).  2 N^2 double FMAs per frame (a bin
+// and its mirror share their products), 0.5 M at N = 512.
+constexpr int kDirectThreads = 256;
+__global__ __launch_bounds__(kDirectThreads) void bf_direct_kernel(BfIn in, BfOut out, int N) {
+  __shared__ double2 w[512];
+  __shared__ float2 xs[512];
+  const long long f = blockIdx.x;
+  for (int n = threadIdx.x; n < N; n += kDirectThreads) {
+    xs[n] = in(f, n);
+    double s, c;
+    sincospi(-2.0 * (double)n / (double)N, &s, &c);
+    w[n] = make_double2(c, s);
+  }
+  __syncthreads();
+  // bins k and N - k share their products (W_N^(n (N - k)) = conj W_N^(n k)):
+  // with W = c + i s,  X[k] = (P - Q) + i (R + S),  X[N - k] = (P + Q) + i (S - R),
+  // P = sum xr c, Q = sum xi s, R = sum xr s, S = sum xi c
+  for (int k = threadIdx.x; 2 * k <= N; k += kDirectThreads) {
+    double P = 0.0, Q = 0.0, R = 0.0, S = 0.0;
+    int m = 0;                                          // n k mod N
+    for (int n = 0; n < N; ++n) {
+      const double2 t = w[m];
+      const double xr = (double)xs[n].x, xi = (double)xs[n].y;
+      P = fma(xr, t.x, P);
+      Q = fma(xi, t.y, Q);
+      R = fma(xr, t.y, R);
+      S = fma(xi, t.x, S);
+      m += k;
+      if (m >= N) m -= N;
+    }
+    out(f, k, make_float2((float)(P - Q), (float)(R + S)));
+    if (k > 0 && 2 * k < N) out(f, N - k, make_float2((float)(P + Q), (float)(S - R)));
   }
 }
 
@@ -498,19 +547,31 @@ hipError_t launch_bf_icol(int N1, int N2, long long batch, float2* tmp, const Bi
 }
 
 hipError_t launch_bf_row(int mode, int N1, int N2, long long batch, float2* tmp, const float2* Bk,
-                         const float2* tw2, float scale, float* psd, int shift, hipStream_t st) {
+                         const float2* tw2, float scale, float* psd, int shift, hipStream_t st,
+                         const BigOut* out) {
   const long long M = (long long)N1 * N2;
+  BfOut bo{};
+  if (out) bo = BfOut{out->dst, out->kind, out->fstride, out->nout, out->chirp, out->conj, out->scale, out->shift};
+  if (mode == 3 && !out) return hipErrorInvalidValue;
   hipError_t e = plan_dispatch(N2, [&](auto plan) {
     using PL = decltype(plan);
     constexpr int F = row_frames<PL>();
     const long long grid = batch * (N1 / F);
     const dim3 g((unsigned)grid), b(F * PL::TF);
-    if (mode == 0) hipLaunchKernelGGL((bf_row_kernel<PL, 0>), g, b, 0, st, tmp, N1, M, Bk, tw2, scale, psd, shift);
-    else if (mode == 1) hipLaunchKernelGGL((bf_row_kernel<PL, 1>), g, b, 0, st, tmp, N1, M, Bk, tw2, scale, psd, shift);
-    else if (mode == 2) hipLaunchKernelGGL((bf_row_kernel<PL, 2>), g, b, 0, st, tmp, N1, M, Bk, tw2, scale, psd, shift);
-    else hipLaunchKernelGGL((bf_row_kernel<PL, 3>), g, b, 0, st, tmp, N1, M, Bk, tw2, scale, psd, shift);
+    if (mode == 0) hipLaunchKernelGGL((bf_row_kernel<PL, 0>), g, b, 0, st, tmp, N1, M, Bk, tw2, scale, psd, shift, bo);
+    else if (mode == 1) hipLaunchKernelGGL((bf_row_kernel<PL, 1>), g, b, 0, st, tmp, N1, M, Bk, tw2, scale, psd, shift, bo);
+    else if (mode == 2) hipLaunchKernelGGL((bf_row_kernel<PL, 2>), g, b, 0, st, tmp, N1, M, Bk, tw2, scale, psd, shift, bo);
+    else hipLaunchKernelGGL((bf_row_kernel<PL, 3>), g, b, 0, st, tmp, N1, M, Bk, tw2, scale, psd, shift, bo);
   });
   return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_bf_direct(int N, long long batch, const BigIn& in, const BigOut& out, hipStream_t st) {
+  if (N < 1 || N > kDirectMax) return hipErrorInvalidValue;
+  BfIn bi{in.src, in.kind, in.fstride, in.estride, in.nvalid, in.chirp, in.win, in.conj, in.scale};
+  BfOut bo{out.dst, out.kind, out.fstride, out.nout, out.chirp, out.conj, out.scale, out.shift};
+  hipLaunchKernelGGL(bf_direct_kernel, dim3((unsigned)batch), dim3(kDirectThreads), 0, st, bi, bo, N);
+  return hipGetLastError();
 }
 
 hipError_t launch_bf_small(int mode, int M, long long batch, const BigIn& in, const BigOut& out,

@@ -2,8 +2,8 @@
 //
 //   mix_c64          apply_frequency_shift (utils.py:120-127): x * exp(j*theta),
 //                    theta = (2*pi*f) * (i / sr) formed in double exactly as numpy
-//                    forms it (once per lane), reduced mod 2*pi in double, sincos
-//                    in fp32, lane-to-element steps from a rotation table
+//                    forms it (for every sample), reduced mod 2*pi in double,
+//                    sincos in fp32
 //   scale_c64        y = x * s (transplant_packet_in_vector's power scale,
 //                    utils.py:1481-1496)
 //   wv_quantize      SMU-WV int16 interleave of mat2wv
@@ -29,41 +29,29 @@ static int ew_grid(long long n) {
 }
 
 // ---------------------------------------------------------------- mixer
-// One tile of 256 x 16 samples per block, sample base + t + 256 e in lane t:
-// the lane forms numpy's phase once (sample base + t, mix_at's exact order),
-// then rotates by exp(j w 256 e / sr) (host table in the kernel arguments,
-// double -> fp32 once): a double division per lane instead of per sample,
-// ~3e-7 relative per sample.
-struct MixTile {
-  float rot[32];   // (cos, sin) of w * 256 e / sr, e < 16, interleaved
-};
-
+// One tile of 256 x 16 samples per block, sample base + t + 256 e in lane t.
+// Every sample forms numpy's phase itself (mix_at: the correctly rounded
+// gi / sr, then w * t, both in double), so the result follows numpy's own
+// rounding of theta at every index: at |theta| ~ 1e10 rad (sample 2^34 at
+// 13 MHz / 56 MHz) one spacing of theta is 4e-6 rad, and a lane that rotated
+// its first sample's phase by a table of exact steps sat up to two spacings
+// (7.8e-6) from numpy's value.  1.5e-7 relative per sample at any offset, and
+// the kernel stays bound by its 16 B per sample: 0.39 ms per 2^27 samples
+// (5.5 TB/s read + write) with the table and without it.
 __global__ __launch_bounds__(256) void mix_c64(const float2* __restrict__ x, long long n, double w,
-                                               double sr, long long i0, float2* __restrict__ y,
-                                               MixTile tab) {
+                                               double sr, long long i0, float2* __restrict__ y) {
   const long long base = (long long)blockIdx.x * 4096 + threadIdx.x;
-  const float2 r0 = mix_at(make_float2(1.f, 0.f), i0 + base, w, sr);
   if (base + 15 * 256 < n) {
     float2 v[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) v[e] = x[base + 256 * e];
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const float2 r = make_float2(r0.x * tab.rot[2 * e] - r0.y * tab.rot[2 * e + 1],
-                                   r0.x * tab.rot[2 * e + 1] + r0.y * tab.rot[2 * e]);
-      const float2 a = v[e];
-      y[base + 256 * e] = make_float2(a.x * r.x - a.y * r.y, a.x * r.y + a.y * r.x);
-    }
+    for (int e = 0; e < 16; ++e) y[base + 256 * e] = mix_at(v[e], i0 + base + 256 * e, w, sr);
   } else {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const long long i = base + 256 * e;
-      if (i < n) {
-        const float2 r = make_float2(r0.x * tab.rot[2 * e] - r0.y * tab.rot[2 * e + 1],
-                                     r0.x * tab.rot[2 * e + 1] + r0.y * tab.rot[2 * e]);
-        const float2 a = x[i];
-        y[i] = make_float2(a.x * r.x - a.y * r.y, a.x * r.y + a.y * r.x);
-      }
+      if (i < n) y[i] = mix_at(x[i], i0 + i, w, sr);
     }
   }
 }
@@ -145,14 +133,8 @@ __global__ __launch_bounds__(256) void c64_to_planar(const float2* __restrict__ 
 // ---------------------------------------------------------------- launchers
 hipError_t launch_mix_c64(const float2* x, long long n, double w, double sr, long long i0, float2* y,
                           hipStream_t st) {
-  MixTile tab;
-  for (int e = 0; e < 16; ++e) {       // w * 256 e / sr reduced mod 2 pi in double
-    const double a = std::remainder(w * (256.0 * e) / sr, 2.0 * M_PI);
-    tab.rot[2 * e] = (float)std::cos(a);
-    tab.rot[2 * e + 1] = (float)std::sin(a);
-  }
   const long long g = (n + 4095) / 4096;
-  hipLaunchKernelGGL(mix_c64, dim3((unsigned)g), dim3(256), 0, st, x, n, w, sr, i0, y, tab);
+  hipLaunchKernelGGL(mix_c64, dim3((unsigned)g), dim3(256), 0, st, x, n, w, sr, i0, y);
   return hipGetLastError();
 }
 

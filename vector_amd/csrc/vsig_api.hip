@@ -540,8 +540,8 @@ int big_plan_fwd(vsig_ctx* c, long long M, const float2* u, long long len, float
   float2* tmp = c->bigtmp.as<float2>();
   vsig::BigIn in{u, 0, 0, 1, len, nullptr, nullptr, 0, 1.0f / (float)M};
   HIPCHK(c, vsig::launch_bf_col(bp.N1, bp.N2, 1, in, tmp, bp.tw1, bp.t2, bp.S, bp.hiA, c->stream));
-  HIPCHK(c, vsig::launch_bf_row(3, bp.N1, bp.N2, 1, tmp, nullptr, bp.tw2, 1.0f,
-                                reinterpret_cast<float*>(S), 0, c->stream));
+  const vsig::BigOut o{S, 0, M, M, nullptr, 0, 1.0f};
+  HIPCHK(c, vsig::launch_bf_row(3, bp.N1, bp.N2, 1, tmp, nullptr, bp.tw2, 1.0f, nullptr, 0, c->stream, &o));
   return VSIG_OK;
 }
 
@@ -595,6 +595,33 @@ int dft_any(vsig_ctx* c, long long N, long long batch, vsig::BigIn in, vsig::Big
     in.conj = out.conj = inverse ? 1 : 0;
     in.nvalid = in.nvalid < N ? in.nvalid : N;
     HIPCHK(c, vsig::launch_bf_small(1, (int)N, batch, in, out, nullptr, tw, c->stream));
+    return VSIG_OK;
+  }
+  // every other length up to 512 points (256 and 512 have gone above): the sum
+  // itself, in double, one block per frame -- exact to the store's rounding,
+  // where a chirp-z of M = 256 .. 1024 points put the engine's error in the
+  // result three times (bigfft.hip: bf_direct_kernel)
+  if (N <= vsig::kDirectMax) {
+    in.conj = out.conj = inverse ? 1 : 0;
+    in.nvalid = in.nvalid < N ? in.nvalid : N;
+    HIPCHK(c, vsig::launch_bf_direct((int)N, batch, in, out, c->stream));
+    return VSIG_OK;
+  }
+  // a longer power of two (up to 2^28) is one four-step transform of N points:
+  // column pass, then the row pass storing natural order through `out` (inverse
+  // by conj at the loads and the stores).  As a chirp-z it was three transforms
+  // of 2N points: max-norm error 2.2 .. 6.9 x complex64 scipy's at 2^15 .. 2^21
+  // against 0.6 .. 2.5 x for the single transform.
+  if (N > 16384 && N <= kBigMax && (N & (N - 1)) == 0) {
+    BigPlan bp;
+    if ((rc = big_plan(c, N, &bp))) return rc;
+    if ((rc = c->bigtmp.reserve(c, (size_t)(batch * N) * sizeof(float2)))) return rc;
+    float2* tmp = c->bigtmp.as<float2>();
+    in.conj = out.conj = inverse ? 1 : 0;
+    in.nvalid = in.nvalid < N ? in.nvalid : N;
+    HIPCHK(c, vsig::launch_bf_col(bp.N1, bp.N2, batch, in, tmp, bp.tw1, bp.t2, bp.S, bp.hiA, c->stream));
+    HIPCHK(c, vsig::launch_bf_row(3, bp.N1, bp.N2, batch, tmp, nullptr, bp.tw2, 1.0f, nullptr, 0, c->stream,
+                                  &out));
     return VSIG_OK;
   }
   vsig_ctx::Chirp* ch;
@@ -872,13 +899,17 @@ int vsig_psd_c64_dev(vsig_ctx* c, const void* x, int64_t n, int64_t stride, cons
     return fail(c, VSIG_E_INVALID, "need 1 <= nperseg <= nfft, hop >= 1, n >= nperseg");
   if (nframes != (n - nperseg) / hop + 1) return fail(c, VSIG_E_INVALID, "nframes mismatch");
   if (!pow2_in(nfft, 64, kBigMax)) {
-    // any other length: Bluestein per frame (bigfft.hip), |X|^2 stored by the
-    // transform's output stage; frames in batches of <= 256 MB of scratch
+    // any other length: a direct sum (<= 512 points) or Bluestein per frame
+    // (bigfft.hip), |X|^2 stored by the transform's output stage; frames in
+    // batches of <= 256 MB of scratch
     if (2LL * nfft - 1 > kBigMax) return fail(c, VSIG_E_UNSUPPORTED, "nfft above 2^27");
-    vsig_ctx::Chirp* ch;
-    int rc = chirp_plan(c, nfft, &ch);
-    if (rc) return rc;
-    long long fb = ch->M <= 16384 ? nframes : (256LL << 20) / (ch->M * 8);
+    int rc;
+    long long fb = nframes;
+    if (nfft > vsig::kDirectMax) {
+      vsig_ctx::Chirp* ch;
+      if ((rc = chirp_plan(c, nfft, &ch))) return rc;
+      if (ch->M > 16384) fb = (256LL << 20) / (ch->M * 8);
+    }
     if (fb < 1) fb = 1;
     Timed t(c, "psd");
     for (long long f0 = 0; f0 < nframes; f0 += fb) {

@@ -68,19 +68,6 @@ struct MixArgs {
   // and lane instead of once per sample.
   float rot[32];     // (cos, sin) interleaved
 };
-__device__ __forceinline__ float2 mix_at(float2 v, long long gi, double w, double sr) {
-  constexpr double kTwoPiHi = 6.28318530717958623200e+00;
-  constexpr double kTwoPiLo = 2.44929359829470635445e-16;
-  constexpr double kInvTwoPi = 1.59154943091895345608e-01;
-  const double t = __ddiv_rn((double)gi, sr);          // np.arange(n) / sample_rate
-  const double th = __dmul_rn(w, t);                   // imaginary part of (2j*pi*f) * t
-  const double k = rint(th * kInvTwoPi);
-  const double r = fma(-k, kTwoPiLo, fma(-k, kTwoPiHi, th));
-  float s, c;
-  sincosf((float)r, &s, &c);
-  return make_float2(v.x * c - v.y * s, v.x * s + v.y * c);
-}
-
 // The fused loads' form: exp(j theta), theta = (w / sr) * gi, one double
 // multiply instead of numpy's division then multiply (|difference| <= ~2 ulp
 // of theta, e.g. 2e-7 rad at |theta| = 1e9 rad; the standalone mixer keeps
@@ -102,6 +89,21 @@ __device__ __forceinline__ float2 cis_rev(double rev) {
   const float c = qi == 0 ? cs : qi == 1 ? -sn : qi == 2 ? -cs : sn;
   const float s = qi == 0 ? sn : qi == 1 ? cs : qi == 2 ? -sn : -cs;
   return make_float2(c, s);
+}
+// The standalone mixer's sample: numpy's theta to the bit (correctly rounded
+// division, then the product), reduced by whole turns in double (Cody-Waite,
+// |r| <= pi to ~1e-16), then cis_rev on r in turns: cheap enough to run for
+// every sample.
+__device__ __forceinline__ float2 mix_at(float2 v, long long gi, double w, double sr) {
+  constexpr double kTwoPiHi = 6.28318530717958623200e+00;
+  constexpr double kTwoPiLo = 2.44929359829470635445e-16;
+  constexpr double kInvTwoPi = 1.59154943091895345608e-01;
+  const double t = __ddiv_rn((double)gi, sr);          // np.arange(n) / sample_rate
+  const double th = __dmul_rn(w, t);                   // imaginary part of (2j*pi*f) * t
+  const double k = rint(th * kInvTwoPi);
+  const double r = fma(-k, kTwoPiLo, fma(-k, kTwoPiHi, th));
+  const float2 e = cis_rev(r * kInvTwoPi);
+  return make_float2(v.x * e.x - v.y * e.y, v.x * e.y + v.y * e.x);
 }
 __device__ __forceinline__ float2 mix_rot_fast(long long gi, double wsr) {
   constexpr double kInvTwoPi = 1.59154943091895345608e-01;
@@ -275,8 +277,13 @@ hipError_t launch_bf_col(int N1, int N2, long long batch, const BigIn& in, float
                          const float2* tw1, const float2* t2, int S, int hiA, hipStream_t st);
 hipError_t launch_bf_icol(int N1, int N2, long long batch, float2* tmp, const BigOut& out,
                           const float2* tw1, const float2* t2, int S, int hiA, hipStream_t st);
+// mode 3 (natural-order DFT output) stores through *out; the other modes ignore it
 hipError_t launch_bf_row(int mode, int N1, int N2, long long batch, float2* tmp, const float2* Bk,
-                         const float2* tw2, float scale, float* psd, int shift, hipStream_t st);
+                         const float2* tw2, float scale, float* psd, int shift, hipStream_t st,
+                         const BigOut* out = nullptr);
+// a frame of N <= kDirectMax points as a direct sum in double (no plan, no chirp)
+constexpr int kDirectMax = 512;
+hipError_t launch_bf_direct(int N, long long batch, const BigIn& in, const BigOut& out, hipStream_t st);
 hipError_t launch_bf_small(int mode, int M, long long batch, const BigIn& in, const BigOut& out,
                            const float2* Bk, const float2* tw, hipStream_t st);
 hipError_t launch_resample_spectrum(const float2* X, long long Nx, long long num, float2* Y,
