@@ -459,6 +459,57 @@ int vsig_peaks_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, doubl
 int vsig_peaks(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, double thr, int32_t relative,
                int64_t min_distance, vsig_instance_t* out, int64_t cap, vsig_peaks_info_t* info);
 
+/* ---- line traces: the lines the reference draws beside every spectrogram --
+ * np.abs(signal) over time (utils.py:551-554, 853-856, 939, 1090) and the
+ * magnitude, or 20 log10 of it, of a whole-capture spectrum over frequency
+ * (vector_analyzer/spectrogram_analysis.py:9-30, analyze_channels.py:6-25,
+ * analyze_vectors.py:17-40, display_vectors.py:26-35, mat_analyzer.py:202-215)
+ * -- reduced on the device to what a plot axis can show: a min / max envelope
+ * per pixel column.
+ * m[i] = |a[i]| exactly as vsig_peak_dev forms it: for complex input numpy's
+ *   abs in the array's own precision (npabs.hpp), for real input fabs.  dtype
+ *   is any VSIG_DTYPE_*.
+ * Position p in [0, n) reads s[p] = m[(p + rot) % n]; with shift != 0
+ *   rot = (n + 1) / 2, which is np.fft.fftshift for even and odd n; without,
+ *   rot = 0.
+ * cols = ceil((hi - lo) / bin); column c covers p in
+ *   [lo + c*bin, min(lo + (c+1)*bin, hi)).
+ * E_min[c] / E_max[c]: the minimum / maximum of s over the column; a NaN
+ *   anywhere in the column makes both NaN (np.min / np.max of that column).
+ * Stored, by kind:
+ *   VSIG_TRACE_ABS   E itself;
+ *   VSIG_TRACE_DB20  20 * log10(E + eps) of the envelope values: the map is
+ *     applied to the 2 * cols results, not per element (log10 and + eps are
+ *     monotone, so the envelope of the mapped line is the mapped envelope).
+ *     Every step is rounded in the output dtype, as vsig_db_dev rounds
+ *     (dbmath.hpp db20_of beside db_of); E + eps == 0 gives -inf.
+ *   At bin = 1 this is the reference's line itself, otherwise its envelope.
+ * Output dtype follows the input: C64 / F32 give float32, C128 / F64 float64.
+ * env_min_dev / env_max_dev hold cols values each; env_min_dev may be NULL
+ *   (bin = 1, where the two planes are equal, or a max-only trace).
+ * info (may be NULL), over [lo, hi): argmax / argmin are the first position p
+ *   of the maximum / minimum of s, in the shifted coordinate and not offset by
+ *   lo; max / min are the stored (mapped) values there.  Arrays that hold NaN
+ *   are outside info's contract; all writes stay inside the three outputs.
+ * The call enqueues on the context stream, never synchronises, allocates
+ * nothing once its scratch is warm for (n, cols), is capturable, and gives the
+ * same bytes for the same input on every run.  a may be any slice of an array
+ * at its element's natural alignment (16-byte loads are used from the first
+ * 16-byte boundary on).
+ * n < 1, n > 2^40, lo < 0, hi > n, lo >= hi, bin < 1, a NULL a or env_max_dev,
+ * an unknown dtype or kind, eps < 0 or not finite: VSIG_E_INVALID before any
+ * work is enqueued. */
+#define VSIG_TRACE_ABS  0   /* |a| */
+#define VSIG_TRACE_DB20 1   /* 20 log10(|a| + eps) */
+typedef struct vsig_trace_info_t {
+  int64_t argmin, argmax;
+  double min, max;
+} vsig_trace_info_t;
+int vsig_trace_envelope_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, int32_t shift,
+                            int64_t lo, int64_t hi, int64_t bin, int32_t kind, double eps,
+                            void* env_min_dev /* may be NULL */, void* env_max_dev,
+                            vsig_trace_info_t* info_dev /* may be NULL */);
+
 /* ---- time-chunk shard of the streaming chain (chain.hip; the C form of
  * vector_amd/shard.py StreamChain; reference precedent: the
  * overlapped chunking of heavy_packet_optimizer.py:114-152).  Rank r of world

@@ -24,5 +24,6 @@ from .analysis import (boxcar_energy, detect_packet_bounds, find_packet_start,  
                        normalize_spectrogram, order_statistics, threshold_stats)
 from .display import (SpectrogramImage, colormap_table, image_extent, plot_spectrogram_image,  # noqa: F401
                       pool_factors, spectrogram_image, spectrogram_levels)
+from .traces import Trace, capture_spectrum, signal_envelope, trace_bin  # noqa: F401
 
 __version__ = "0.1.0"

@@ -77,6 +77,14 @@ class PeaksInfo(C.Structure):
     _fields_ = [("count", I64), ("argmax", I64), ("max", C.c_double), ("thr_used", C.c_double)]
 
 
+class TraceInfo(C.Structure):
+    """vsig_trace_info_t (include/vsig.h)."""
+    _fields_ = [("argmin", I64), ("argmax", I64), ("min", C.c_double), ("max", C.c_double)]
+
+
+TRACE_ABS, TRACE_DB20 = 0, 1
+
+
 # name -> (restype, argtypes); every symbol include/vsig.h declares.
 SIGNATURES = {
     "vsig_version": (C.c_int, []),
@@ -126,6 +134,7 @@ SIGNATURES = {
     "vsig_abs_stats_dev": (C.c_int, [P, I32, P, I64, P]),
     "vsig_correlate_stats_dev": (C.c_int, [P, I32, P, I64, P, I64, I32, P]),
     "vsig_region_power_dev": (C.c_int, [P, P, P, I64, P]),
+    "vsig_trace_envelope_dev": (C.c_int, [P, I32, P, I64, I32, I64, I64, I64, I32, C.c_double, P, P, P]),
     "vsig_mix_c64_dev": (C.c_int, [P, P, I64, C.c_double, C.c_double, I64, P]),
     "vsig_scale_c64_dev": (C.c_int, [P, P, I64, C.c_float, P]),
     "vsig_wv_quantize_dev": (C.c_int, [P, P, I64, C.c_float, P]),

@@ -90,6 +90,7 @@ struct vsig_ctx {
   DevBuf sscratch;                       // np_stats buffer sums
   DevBuf pscratch;                       // peaks.hip tile table, counts, offsets
   DevBuf gscratch;                       // region.hip per-block partials
+  DevBuf tscratch;                       // trace.hip per-block / per-chunk / per-column records
   PeakPartial* parts() const { return partials.as<PeakPartial>(); }
   // the first-level buffer of a two-level finalize, right after the partials,
   // then the fused finalize's block counters (zero between launches)
@@ -1524,6 +1525,31 @@ int vsig_region_power_dev(vsig_ctx* c, const void* a, const void* b, int64_t n, 
   Timed t(c, "region_power");
   HIPCHK(c, vsig::launch_region_power(static_cast<const float2*>(a), static_cast<const float2*>(b), n,
                                       sums_dev, c->gscratch.data(), c->stream));
+  return VSIG_OK;
+}
+
+// ---------------------------------------------------------------- line traces
+static_assert(sizeof(vsig_trace_info_t) == sizeof(vsig::TraceInfo) && sizeof(vsig_trace_info_t) == 32,
+              "vsig_trace_info_t layout");
+static_assert(VSIG_TRACE_ABS == vsig::kTraceAbs && VSIG_TRACE_DB20 == vsig::kTraceDb20, "VSIG_TRACE_*");
+
+int vsig_trace_envelope_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, int32_t shift, int64_t lo,
+                            int64_t hi, int64_t bin, int32_t kind, double eps, void* env_min_dev,
+                            void* env_max_dev, vsig_trace_info_t* info_dev) {
+  if (!c || !a || !env_max_dev) return fail(c, VSIG_E_INVALID, "null pointer");
+  if (n < 1) return fail(c, VSIG_E_INVALID, "empty input");
+  if (n > (1LL << 40)) return fail(c, VSIG_E_INVALID, "n above 2^40");
+  if (dtype < VSIG_DTYPE_C128 || dtype > VSIG_DTYPE_F32) return fail(c, VSIG_E_INVALID, "dtype");
+  if (kind != VSIG_TRACE_ABS && kind != VSIG_TRACE_DB20) return fail(c, VSIG_E_INVALID, "kind");
+  if (lo < 0 || hi > n || lo >= hi) return fail(c, VSIG_E_INVALID, "need 0 <= lo < hi <= n");
+  if (bin < 1) return fail(c, VSIG_E_INVALID, "need bin >= 1");
+  if (!(eps >= 0.0) || std::isinf(eps)) return fail(c, VSIG_E_INVALID, "need a finite eps >= 0");
+  int rc = c->tscratch.reserve(c, vsig::trace_scratch_bytes(lo, hi, bin));
+  if (rc) return rc;
+  Timed t(c, "trace");
+  HIPCHK(c, vsig::launch_trace_envelope(dtype, a, n, shift != 0, lo, hi, bin, kind, eps, env_min_dev,
+                                        env_max_dev, reinterpret_cast<vsig::TraceInfo*>(info_dev),
+                                        c->tscratch.data(), c->stream));
   return VSIG_OK;
 }
 

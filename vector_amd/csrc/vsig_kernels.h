@@ -364,4 +364,17 @@ size_t peaks_scratch_bytes(long long n);
 hipError_t launch_peaks(int dtype, const void* a, long long n, double thr, int relative, long long d,
                         PeakInst* out, long long cap, PeaksInfo* info, void* scratch, hipStream_t st);
 
+// trace.hip: the min / max envelope of |a| per column of `bin` positions of
+// the (optionally fftshifted) line over [lo, hi), and the window's first
+// extrema (vsig_trace_envelope_dev; see include/vsig.h).  env_min / info may
+// be null.  scratch: trace_scratch_bytes(lo, hi, bin).
+constexpr int kTraceTile = 2048;             // positions a block of trace_cols owns at most
+constexpr int kTraceAbs = 0, kTraceDb20 = 1;                                 // = VSIG_TRACE_*
+struct TraceRec { double mn, mx; long long pmn, pmx, nan; };                 // one block's / column's extrema
+struct TraceInfo { long long argmin, argmax; double min, max; };             // = vsig_trace_info_t
+size_t trace_scratch_bytes(long long lo, long long hi, long long bin);
+hipError_t launch_trace_envelope(int dtype, const void* a, long long n, int shift, long long lo,
+                                 long long hi, long long bin, int kind, double eps, void* env_min,
+                                 void* env_max, TraceInfo* info, void* scratch, hipStream_t st);
+
 }  // namespace vsig
