@@ -119,7 +119,9 @@ def _percentile(n, pct, dt, fetch):
     """np.percentile(arr, pct) (method 'linear') for an array of n elements
     of dtype dt, given fetch(ranks) -> k-th smallest values.  Mirrors numpy's
     _quantile / _get_indexes / _get_gamma / _lerp including the dtype the
-    arithmetic runs in (float32 arrays interpolate in float32)."""
+    arithmetic runs in (float32 arrays interpolate in float32), and its NaN
+    rule: NaN sorts last, so a NaN largest element means one is present and
+    the result is NaN (the last rank rides in the same select call)."""
     dt = np.dtype(dt)
     q = np.asanyarray(np.true_divide(pct, dt.type(100)))
     if np.any(q < 0) or np.any(q > 1):
@@ -134,7 +136,9 @@ def _percentile(n, pct, dt, fetch):
     if np.isnan(virtual):
         prev, nxt = np.asanyarray(-1), np.asanyarray(-1)
     pi, ni = int(prev) % n, int(nxt) % n
-    vals = fetch(sorted({pi, ni}))
+    vals = fetch(sorted({pi, ni, n - 1}))
+    if np.isnan(vals[n - 1]):
+        return np.asarray(np.nan, dtype=dt)[()]
     a = np.asarray(vals[pi], dtype=dt)
     b = np.asarray(vals[ni], dtype=dt)
     gamma = np.asanyarray(virtual - prev.astype(np.intp), dtype=virtual.dtype)
@@ -146,13 +150,16 @@ def _percentile(n, pct, dt, fetch):
 
 
 def _median(n, dt, fetch):
-    """np.median of n elements of dtype dt from order statistics."""
+    """np.median of n elements of dtype dt from order statistics (NaN when the
+    largest element is NaN, i.e. when any is)."""
     if n == 0:
         return np.dtype(dt).type(np.nan)
     k = n // 2
+    v = fetch(sorted({k, n - 1} if n % 2 else {k - 1, k, n - 1}))
+    if np.isnan(v[n - 1]):
+        return np.dtype(dt).type(np.nan)
     if n % 2:
-        return np.dtype(dt).type(fetch([k])[k])
-    v = fetch([k - 1, k])
+        return np.dtype(dt).type(v[k])
     return np.mean(np.array([v[k - 1], v[k]], dtype=dt))
 
 
@@ -188,9 +195,12 @@ def _select_levels(Sxx, low_percentile, high_percentile, max_dynamic_range):
 
     # |S| > 0 count: |S| >= the smallest subnormal of the dtype
     tiny = float(np.finfo(dt).smallest_subnormal)
-    npos, _, _, _ = _thresh_dev(ctx, t, code, tiny)
+    npos, _, _, mx = _thresh_dev(ctx, t, code, tiny)
+    # np.max is NaN exactly when an element is; they sort last and are counted
+    # only then (|S| >= 0 is false for a NaN alone)
+    nnan = n - _thresh_dev(ctx, t, code, 0.0)[0] if np.isnan(mx) else 0
     if npos > 0:
-        nzero = n - npos
+        nzero = n - npos - nnan
         noise_floor = _percentile(npos, 5, dt, lambda rk: fetch(rk, nzero))
     else:
         noise_floor = 1e-12
@@ -205,13 +215,19 @@ def _select_levels(Sxx, low_percentile, high_percentile, max_dynamic_range):
     def fetch_db(ranks):
         return {r: db_of(v) for r, v in fetch(ranks).items()}
 
+    def min_max_db():
+        """np.min / np.max of the dB map (both NaN when an element is)."""
+        if nnan:
+            return db_of(np.nan)[()], db_of(np.nan)[()]
+        return db_of(fetch([0])[0])[()], db_of(fetch([n - 1])[n - 1])[()]
+
     try:
         vmin = _percentile(n, low_percentile, db_dt, fetch_db)
         vmax = _percentile(n, high_percentile, db_dt, fetch_db)
     except Exception:
-        vmin, vmax = db_of(fetch([0])[0])[()], db_of(fetch([n - 1])[n - 1])[()]
+        vmin, vmax = min_max_db()
     if np.isnan(vmin) or np.isnan(vmax) or vmax <= vmin:
-        vmin, vmax = db_of(fetch([0])[0])[()], db_of(fetch([n - 1])[n - 1])[()]
+        vmin, vmax = min_max_db()
         if vmax <= vmin:
             vmax = vmin + max_dynamic_range
     actual_range = vmax - vmin

@@ -5,7 +5,8 @@
 //                   np.percentile / np.median), 8-bit digits of order-preserving
 //                   keys of float32 / float64 data
 //   thresh_reduce   count / first / last index with value >= threshold, max
-//                   (np.where(sm >= thr)[0][0 / -1], np.max)
+//                   (np.where(sm >= thr)[0][0 / -1], np.max: NaN when any
+//                   element is)
 //   energy_scan     inclusive prefix sums of |x|^2 in double (3 kernels)
 //   boxcar_same     np.convolve(e, ones(w)/w, 'same') from the prefix sums
 //   db_transform    10*log10(|S| + floor) in double (normalize_spectrogram)
@@ -86,6 +87,9 @@ struct ThreshPartial {
   double max;
 };
 
+// np.max's step: a NaN wins and then stays (nothing compares above it).
+__device__ __forceinline__ double np_max(double m, double v) { return (v > m || v != v) ? v : m; }
+
 template <class T>
 __global__ __launch_bounds__(256) void thresh_reduce(const T* __restrict__ a, long long n, double thr,
                                                      ThreshPartial* __restrict__ parts) {
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(256) void thresh_reduce(const T* __restrict__ a, lo
       if (i < first) first = i;
       if (i > last) last = i;
     }
-    mx = v > mx ? v : mx;
+    mx = np_max(mx, v);
   }
   for (int off = 32; off > 0; off >>= 1) {
     cnt += __shfl_xor(cnt, off);
@@ -107,7 +111,7 @@ __global__ __launch_bounds__(256) void thresh_reduce(const T* __restrict__ a, lo
     const double m2 = __shfl_xor(mx, off);
     first = f2 < first ? f2 : first;
     last = l2 > last ? l2 : last;
-    mx = m2 > mx ? m2 : mx;
+    mx = np_max(mx, m2);
   }
   __shared__ ThreshPartial w[4];
   if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = ThreshPartial{cnt, first, last, mx};
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(256) void thresh_reduce(const T* __restrict__ a, lo
       r.count += w[q].count;
       r.first = w[q].first < r.first ? w[q].first : r.first;
       r.last = w[q].last > r.last ? w[q].last : r.last;
-      r.max = w[q].max > r.max ? w[q].max : r.max;
+      r.max = np_max(r.max, w[q].max);
     }
     parts[blockIdx.x] = r;
   }
@@ -232,6 +236,25 @@ __global__ __launch_bounds__(256) void boxcar_same(const double* __restrict__ P,
   }
 }
 
+// The same outputs summed directly over each window, for an input with a
+// non-finite energy: every prefix sum after it is inf or NaN, and their
+// differences with it, where np.convolve is non-finite inside the window
+// alone.  O(n w), so it runs only when the last prefix sum is not finite.
+template <class T>
+__global__ __launch_bounds__(256) void boxcar_direct(const T* __restrict__ x, long long n, long long w,
+                                                     long long nout, long long c,
+                                                     double* __restrict__ sm) {
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nout; i += stride) {
+    long long hi = i + c, lo = i + c - w + 1;          // inclusive window
+    if (hi > n - 1) hi = n - 1;
+    if (lo < 0) lo = 0;
+    double acc = 0.0;
+    for (long long k = lo; k <= hi; ++k) acc += energy_of(x, k);
+    sm[i] = acc / (double)w;
+  }
+}
+
 // ---------------------------------------------------------------- dB / abs
 // normalize_spectrogram's 10 * np.log10(|S| + floor) in the dtype numpy
 // evaluates it in (float32 S with a float32 floor stays float32): db_of
@@ -327,6 +350,21 @@ hipError_t launch_boxcar_same(const double* P, long long n, long long w, double*
   const long long nout = n > w ? n : w;
   const long long c = ((n < w ? n : w) - 1) / 2;
   hipLaunchKernelGGL(boxcar_same, dim3(grid_for(nout)), dim3(256), 0, st, P, n, w, nout, c, sm);
+  return hipGetLastError();
+}
+
+hipError_t launch_boxcar_direct(int dtype, const void* x, long long n, long long w, double* sm,
+                                hipStream_t st) {
+  const long long nout = n > w ? n : w;
+  const long long c = ((n < w ? n : w) - 1) / 2;
+  const dim3 g(grid_for(nout)), b(256);
+  switch (dtype) {
+    case VSIG_C128: hipLaunchKernelGGL(boxcar_direct<double2>, g, b, 0, st, (const double2*)x, n, w, nout, c, sm); break;
+    case VSIG_C64: hipLaunchKernelGGL(boxcar_direct<float2>, g, b, 0, st, (const float2*)x, n, w, nout, c, sm); break;
+    case VSIG_F64: hipLaunchKernelGGL(boxcar_direct<double>, g, b, 0, st, (const double*)x, n, w, nout, c, sm); break;
+    case VSIG_F32: hipLaunchKernelGGL(boxcar_direct<float>, g, b, 0, st, (const float*)x, n, w, nout, c, sm); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

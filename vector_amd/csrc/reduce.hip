@@ -35,6 +35,48 @@ __global__ __launch_bounds__(256) void peak_reduce(const T* __restrict__ a, long
   block_partial<256>(m, mi, s1, s2, partials + blockIdx.x);
 }
 
+// np.argmax / np.max take a NaN for the maximum, the first one at that, and
+// betterd never takes one (the correlators' reductions share it and stay as
+// they are).  The record's sum |a| is NaN exactly when some |a| is -- |a| >= 0,
+// so an inf alone sums to inf -- and finite input therefore costs this launch
+// one 8-byte read.  Otherwise one block finds the first NaN.
+template <class T>
+__global__ __launch_bounds__(1024) void peak_first_nan(const T* __restrict__ a, long long n,
+                                                       PeakPartial* __restrict__ rec) {
+  if (rec->sum_abs == rec->sum_abs) return;              // uniform: every thread reads the same word
+  long long first = 0x7fffffffffffffffLL;
+  for (long long i = threadIdx.x; i < n; i += 1024) {
+    const double v = absval<T>(a, i);
+    if (v != v) { first = i; break; }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const long long o = __shfl_xor(first, off);
+    first = o < first ? o : first;
+  }
+  __shared__ long long sf[16];
+  if ((threadIdx.x & 63) == 0) sf[threadIdx.x >> 6] = first;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int q = 1; q < 16; ++q) first = sf[q] < first ? sf[q] : first;
+    if (first < n) {
+      rec->max2 = __builtin_nan("");
+      rec->idx = first;
+    }
+  }
+}
+
+hipError_t launch_peak_first_nan(int dtype, const void* a, long long n, PeakPartial* rec, hipStream_t st) {
+  switch (dtype) {
+    case VSIG_C128: hipLaunchKernelGGL(peak_first_nan<double2>, dim3(1), dim3(1024), 0, st, (const double2*)a, n, rec); break;
+    case VSIG_C64: hipLaunchKernelGGL(peak_first_nan<float2>, dim3(1), dim3(1024), 0, st, (const float2*)a, n, rec); break;
+    case VSIG_F64: hipLaunchKernelGGL(peak_first_nan<double>, dim3(1), dim3(1024), 0, st, (const double*)a, n, rec); break;
+    case VSIG_F32: hipLaunchKernelGGL(peak_first_nan<float>, dim3(1), dim3(1024), 0, st, (const float*)a, n, rec); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 // Fixed-order reduction of nparts partials into out[0]; sqrt_max converts a
 // max |c|^2 into max |c|.
 __global__ __launch_bounds__(1024) void partial_finalize(const PeakPartial* __restrict__ parts,

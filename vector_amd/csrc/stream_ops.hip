@@ -97,17 +97,23 @@ __device__ __forceinline__ short np_f32_to_i16(float f) {
   return (short)(v & 0xffff);
 }
 
-// norm > 0: signal / norm first, then * 32767 in float32, as mat2wv does.
-// numpy divides a complex64 by a real scalar with Smith's formula, which for
-// a zero imaginary divisor is a multiply by the rounded reciprocal 1/norm.
+// norm > 0 or NaN (the peak of a signal that holds one): signal / norm first,
+// then * 32767 in float32, as mat2wv does.  numpy has no complex-by-real
+// loops: the scalar becomes a complex with a zero imaginary part.  Dividing by
+// it is Smith's formula, which is then a multiply by the rounded reciprocal
+// 1/norm, and each part also takes the other part times that zero -- nothing
+// for a finite part, NaN for an infinite or NaN one.  The multiply by 32767
+// (a complex 32767 + 0j to numpy) has the same cross terms.
 __global__ __launch_bounds__(256) void wv_quantize(const float2* __restrict__ x, long long n, float norm,
                                                    short2* __restrict__ out) {
   const long long stride = (long long)gridDim.x * 256;
-  const float rcp = norm > 0.f ? __fdiv_rn(1.f, norm) : 1.f;
+  const bool div = norm > 0.f || norm != norm;
+  const float rcp = div ? __fdiv_rn(1.f, norm) : 1.f;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     float2 v = x[i];
-    if (norm > 0.f) v = make_float2(v.x * rcp, v.y * rcp);
-    out[i] = make_short2(np_f32_to_i16(v.x * 32767.f), np_f32_to_i16(v.y * 32767.f));
+    if (div) v = make_float2((v.x + v.y * 0.f) * rcp, (v.y - v.x * 0.f) * rcp);
+    out[i] = make_short2(np_f32_to_i16(v.x * 32767.f - v.y * 0.f),
+                         np_f32_to_i16(v.x * 0.f + v.y * 32767.f));
   }
 }
 

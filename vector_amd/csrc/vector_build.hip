@@ -152,8 +152,14 @@ __global__ __launch_bounds__(kVbThreads) void vector_build(PlaceBatch pb, float2
 
 // numpy divides a complex64 by a float32 scalar with Smith's formula, which for
 // a zero imaginary divisor is a multiply of both parts by the rounded
-// reciprocal (see wv_quantize, stream_ops.hip).  Same alignment scheme as
-// vector_build when x and y share their 16-byte phase (in place: always).
+// reciprocal, after each part has taken the other part times that zero
+// (nothing for a finite part, NaN for an infinite or NaN one: with an infinite
+// peak the sample that holds it becomes NaN in both parts; see wv_quantize,
+// stream_ops.hip).  Same alignment scheme as vector_build when x and y share
+// their 16-byte phase (in place: always).
+__device__ __forceinline__ float2 np_div_real(float2 v, float r) {
+  return make_float2((v.x + v.y * 0.f) * r, (v.y - v.x * 0.f) * r);
+}
 template <bool V4>
 __global__ __launch_bounds__(256) void normalize_c64(const float2* x, long long n,
                                                      const float* __restrict__ maxabs, float2* y,
@@ -168,23 +174,26 @@ __global__ __launch_bounds__(256) void normalize_c64(const float2* x, long long 
       const long long p0 = 2 * j - head;
       if (p0 >= 0 && p0 + 1 < n) {
         vb_f4 v = *reinterpret_cast<const vb_f4*>(x + p0);
-        if (on) v = vb_f4{v.x * r, v.y * r, v.z * r, v.w * r};
+        if (on) {
+          const float2 p = np_div_real(make_float2(v.x, v.y), r), q = np_div_real(make_float2(v.z, v.w), r);
+          v = vb_f4{p.x, p.y, q.x, q.y};
+        }
         __builtin_nontemporal_store(v, reinterpret_cast<vb_f4*>(y + p0));
       } else {
         if (p0 >= 0 && p0 < n) {
           const float2 v = x[p0];
-          y[p0] = on ? make_float2(v.x * r, v.y * r) : v;
+          y[p0] = on ? np_div_real(v, r) : v;
         }
         if (p0 + 1 < n) {
           const float2 v = x[p0 + 1];
-          y[p0 + 1] = on ? make_float2(v.x * r, v.y * r) : v;
+          y[p0 + 1] = on ? np_div_real(v, r) : v;
         }
       }
     }
   } else {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
       const float2 v = x[i];
-      y[i] = on ? make_float2(v.x * r, v.y * r) : v;
+      y[i] = on ? np_div_real(v, r) : v;
     }
   }
 }

@@ -1440,7 +1440,10 @@ int vsig_peak_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, vsig_pea
     Timed t(c, "peak");
     HIPCHK(c, vsig::launch_peak_reduce(dtype, a, n, c->parts(), (int)nparts, c->stream));
   }
-  return finalize_peak(c, nparts, 0, peak_dev);
+  if ((rc = finalize_peak(c, nparts, 0, peak_dev))) return rc;
+  // numpy's answer when the array holds a NaN (a no-op on any other record)
+  HIPCHK(c, vsig::launch_peak_first_nan(dtype, a, n, peak_record(c, peak_dev), c->stream));
+  return VSIG_OK;
 }
 
 int vsig_peak(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, vsig_peak_t* peak) {
@@ -1786,7 +1789,7 @@ int vsig_threshold_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, dou
     cnt += p.count;
     f = p.first < f ? p.first : f;
     l = p.last > l ? p.last : l;
-    mx = p.max > mx ? p.max : mx;
+    mx = (p.max > mx || p.max != p.max) ? p.max : mx;     // np.max: a NaN wins and stays
   }
   *count = cnt;
   *first = f;
@@ -1806,7 +1809,15 @@ int vsig_boxcar_energy_dev(vsig_ctx* c, int32_t dtype, const void* x, int64_t n,
   double* P = c->stage[2].as<double>();
   HIPCHK(c, vsig::launch_energy_prefix(dtype, x, n, c->stage[1].as<double>(), P, c->stream));
   HIPCHK(c, vsig::launch_boxcar_same(P, n, w, sm, c->stream));
+  double last = 0.0;
+  HIPCHK(c, hipMemcpyAsync(&last, P + (n - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));   // stage buffers are reused by the next call
+  if (!std::isfinite(last)) {
+    // a non-finite energy poisons every prefix sum after it: np.convolve is
+    // non-finite inside the window alone, so the outputs are summed directly
+    HIPCHK(c, vsig::launch_boxcar_direct(dtype, x, n, w, sm, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
   return VSIG_OK;
 }
 

@@ -174,6 +174,9 @@ hipError_t launch_copy_probe(const float2* x, long long n, float2* y, int varian
 #endif
 hipError_t launch_peak_reduce(int dtype, const void* a, long long n, PeakPartial* partials,
                               int nparts, hipStream_t st);
+// np.argmax / np.max of an array holding a NaN: rec (peak_reduce's finalized record) gets
+// the first NaN's index and a NaN maximum; a record whose sum |a| is not NaN is left alone
+hipError_t launch_peak_first_nan(int dtype, const void* a, long long n, PeakPartial* rec, hipStream_t st);
 constexpr int kFinalizeTmp = 1024;   // first-level partials of a two-level finalize
 // zeroed PeakPartial-sized slots after the kFinalizeTmp records: the
 // finalize's counter (first 8 B) and refine_fused's counters (128 B)
@@ -338,6 +341,9 @@ long long energy_scan_tiles(long long n);
 hipError_t launch_energy_prefix(int dtype, const void* x, long long n, double* sums, double* P,
                                 hipStream_t st);
 hipError_t launch_boxcar_same(const double* P, long long n, long long w, double* sm, hipStream_t st);
+// the same outputs summed directly over each window (an input with a non-finite energy)
+hipError_t launch_boxcar_direct(int dtype, const void* x, long long n, long long w, double* sm,
+                                hipStream_t st);
 hipError_t launch_db_transform(int dtype, const void* a, long long n, double floor_, void* out,
                                hipStream_t st);
 hipError_t launch_abs_c64(int dtype, const void* a, long long n, float2* out, hipStream_t st);

@@ -671,9 +671,10 @@ def find_peaks(a, threshold, min_distance=0, relative=False, max_peaks=65536):
     neighbour within min_distance is dropped even if that neighbour is itself
     dropped.  Two peaks are more than min_distance apart; min_distance=0 keeps
     every element at or above the threshold; a flat array has the one peak 0;
-    relative=True with threshold 1.0 returns np.argmax's index alone.  NaN
-    elements are outside the contract (they are never peaks and never
-    suppress one).
+    relative=True with threshold 1.0 returns np.argmax's index alone.  A NaN
+    magnitude counts as -1: it is never a peak, never suppresses one and
+    never becomes the maximum (unlike np.argmax, which takes the first NaN;
+    an array of nothing but NaN has count 0, argmax 0 and max -1).
 
     numpy in -> ``(indices int64[k], values float64[k])``; with more than
     max_peaks peaks a RuntimeWarning and the first max_peaks.  CUDA tensor in
