@@ -9,6 +9,9 @@
  *   vsig_psd_*        scipy.signal.spectrogram(..., return_onesided=False,
  *                     detrend=False, scaling='spectrum')      utils.py:281-291
  *                     (+ fftshift of Sxx, utils.py:351, when shift = 1)
+ *   vsig_psd_traces_* the mean / max / min of that Sxx over its frames
+ *                     (scipy.signal.welch(..., average='mean'), max-hold,
+ *                     min-hold) without storing it
  *   vsig_fir_*        np.convolve(x, taps, 'full')[:len(x)] then x[::decim]
  *                     (reference idioms utils.py:802,816 and utils.py:194)
  *   vsig_correlate_*  np.correlate(signal2, signal1, mode) in
@@ -136,7 +139,10 @@ int vsig_synchronize(vsig_ctx* ctx);
  *                     correlated stream before that.  The library itself joins
  *                     before it reuses the refine's scratch (any later
  *                     correlation, peak, statistics or staging call), and
- *                     vsig_refine_status / vsig_synchronize wait for it. */
+ *                     vsig_refine_status / vsig_synchronize wait for it.
+ * and of the spectrum traces (vsig_psd_traces_c64_dev):
+ *   "psd_traces_batch" 0 (default): frames per stored batch by the 256 MB rule;
+ *                     > 0: at most that many (nfft outside the in-LDS plans only). */
 int vsig_set_option(vsig_ctx* ctx, const char* key, int value);
 int vsig_get_option(const vsig_ctx* ctx, const char* key, int* value);
 /* The hipStream_t the "refine_async" refine runs on (the context stream when
@@ -189,6 +195,43 @@ int vsig_psd_c64_dev(vsig_ctx* ctx, const void* x, int64_t n, int64_t stride, co
 int vsig_psd_c64(vsig_ctx* ctx, const void* x, int64_t n, const float* win, int32_t nperseg,
                  int64_t hop, int32_t nfft, float scale, int32_t shift, float* sxx,
                  int64_t nframes);
+
+/* ---- spectrum traces: per-bin mean / max-hold / min-hold of Sxx over its frames in one
+ * pass (a spectrum analyser's averaged, max-hold and min-hold detectors; the mean is
+ * scipy.signal.welch(..., average='mean') with vsig_psd_*'s arguments).  The spectrogram
+ * is never stored: the call reads 8 bytes per sample and writes O(nfft).
+ * Arguments, validation and the frames are vsig_psd_c64_dev's.  With P[m][k] the float32
+ * value vsig_psd_c64_dev stores for frame m, bin k (the same expression on the same
+ * transform), at (k + nfft/2) % nfft when shift = 1:
+ *   max[k]  = max over m, min[k] = min over m                       float32[nfft]
+ *   mean[k] = (sum over m of (double)P[m][k]) / nframes             float64[nfft]
+ * The sum is kept in double in registers, records and merge, so the result depends on the
+ * launch geometry by about nframes * 2^-53 relative only.  A NaN P[m][k] makes all three
+ * outputs of bin k NaN (np.max / np.min / np.mean).  Any output may be NULL (not computed);
+ * all three NULL is VSIG_E_INVALID.
+ * The call enqueues on the context stream and never synchronises; once its scratch (a
+ * grow-only context buffer, bounded by the device's CU count and nfft, not by nframes) is
+ * warm it allocates nothing and can be captured into a graph.  No float atomics; the
+ * launch geometry is a function of (nfft, nframes) and the device alone, so the same input
+ * gives the same bytes on every run.
+ * nfft 64 .. 8192 (powers of two): the transform kernels reduce in their epilogue.  Every
+ * other nfft vsig_psd_c64_dev accepts (16384 among them: its accumulators fit neither the
+ * registers nor the LDS its transform leaves): that route runs in batches of frames into a
+ * bounded scratch (256 MB, or at most "psd_traces_batch" frames: a vsig_set_option key,
+ * 0 = automatic, the default) and each batch is folded into the same records.
+ * vsig_psd_traces_plan: the geometry for (nfft, nframes) on the current device.  In-LDS
+ * lengths: `blocks` blocks, block b owns the frames [b * frames_per_block, (b + 1) *
+ * frames_per_block) and transforms frames_per_block_step of them at a time.  Other lengths:
+ * blocks = the record rows the batches fold into, step 1, frames_per_block 0 (the frames
+ * are interleaved over the rows). */
+int vsig_psd_traces_c64_dev(vsig_ctx* ctx, const void* x, int64_t n, int64_t stride, const float* win,
+                            int32_t nperseg, int64_t hop, int32_t nfft, float scale, int32_t shift,
+                            int64_t nframes, double* mean_dev, float* max_dev, float* min_dev);
+int vsig_psd_traces_c64(vsig_ctx* ctx, const void* x, int64_t n, const float* win, int32_t nperseg,
+                        int64_t hop, int32_t nfft, float scale, int32_t shift, int64_t nframes,
+                        double* mean, float* max, float* min);
+int vsig_psd_traces_plan(int32_t nfft, int64_t nframes, int64_t* blocks, int64_t* frames_per_block_step,
+                         int64_t* frames_per_block);
 
 /* ---- FIR: y[g] = sum_{m<ntaps} h[m] x[g*decim - m] (x = 0 outside [0, n)),
  * g in [0, ceil(n/decim)).  Taps complex64 on the host (real taps: imag = 0);

@@ -8,7 +8,7 @@ a HIP device every call raises ``VsigUnavailable``.
 from ._lib import (RefineFault, VsigError, VsigInvalid, VsigUnavailable, get_context,  # noqa: F401
                    load_library)
 from . import dsp  # noqa: F401
-from .dsp import (Correlator, FirFilter, correlate, correlate_peak,  # noqa: F401
+from .dsp import (Correlator, FirFilter, SpectrumTraces, averaged_spectrum, correlate, correlate_peak,  # noqa: F401
                   cross_correlate_signals, filter, find_correlation_peak,
                   find_packet_instances, find_packet_location_in_vector, find_peaks, fir_filter,
                   peak_stats, spectrum)
@@ -24,6 +24,6 @@ from .analysis import (boxcar_energy, detect_packet_bounds, find_packet_start,  
                        normalize_spectrogram, order_statistics, threshold_stats)
 from .display import (SpectrogramImage, colormap_table, image_extent, plot_spectrogram_image,  # noqa: F401
                       pool_factors, spectrogram_image, spectrogram_levels)
-from .traces import Trace, capture_spectrum, signal_envelope, trace_bin  # noqa: F401
+from .traces import Trace, averaged_spectrum_trace, capture_spectrum, signal_envelope, trace_bin  # noqa: F401
 
 __version__ = "0.1.0"

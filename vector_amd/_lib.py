@@ -109,6 +109,9 @@ SIGNATURES = {
     "vsig_clock_read": (C.c_int, [P, C.c_char_p, C.POINTER(C.c_double), C.POINTER(I64)]),
     "vsig_psd_c64_dev": (C.c_int, [P, P, I64, I64, P, I32, I64, I32, F32, I32, P, I64]),
     "vsig_psd_c64": (C.c_int, [P, P, I64, P, I32, I64, I32, F32, I32, P, I64]),
+    "vsig_psd_traces_c64_dev": (C.c_int, [P, P, I64, I64, P, I32, I64, I32, F32, I32, I64, P, P, P]),
+    "vsig_psd_traces_c64": (C.c_int, [P, P, I64, P, I32, I64, I32, F32, I32, I64, P, P, P]),
+    "vsig_psd_traces_plan": (C.c_int, [I32, I64, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]),
     "vsig_fir_create": (C.c_int, [P, P, I32, I32, C.POINTER(P)]),
     "vsig_fir_free": (None, [P]),
     "vsig_fir_exec_dev": (C.c_int, [P, P, I64, P, I64]),

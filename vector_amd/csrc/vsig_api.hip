@@ -91,6 +91,8 @@ struct vsig_ctx {
   DevBuf pscratch;                       // peaks.hip tile table, counts, offsets
   DevBuf gscratch;                       // region.hip per-block partials
   DevBuf tscratch;                       // trace.hip per-block / per-chunk / per-column records
+  DevBuf ptscratch;                      // psd_traces.hip record rows (+ the fold route's frame batch)
+  long long psd_traces_batch = 0;        // fold route: frames per batch at most (0: the 256 MB rule)
   PeakPartial* parts() const { return partials.as<PeakPartial>(); }
   // the first-level buffer of a two-level finalize, right after the partials,
   // then the fused finalize's block counters (zero between launches)
@@ -744,6 +746,9 @@ int vsig_set_option(vsig_ctx* c, const char* key, int value) {
   } else if (k == "blas_threads") {
     if (value < 1 || value > 1024) return fail(c, VSIG_E_INVALID, "blas_threads must be in [1, 1024]");
     c->blas_threads = value;
+  } else if (k == "psd_traces_batch") {
+    if (value < 0) return fail(c, VSIG_E_INVALID, "psd_traces_batch must be >= 0");
+    c->psd_traces_batch = value;
   } else if (k == "refine_async") {
     vsig_ctx::RefineAsync& ra = c->ra;
     if (value && !ra.stream) {
@@ -773,6 +778,7 @@ int vsig_get_option(const vsig_ctx* c, const char* key, int* value) {
   else if (k == "refine_watchdog_us") *value = (int)c->refine_wd_us;
   else if (k == "blas_threads") *value = c->blas_threads;
   else if (k == "refine_async") *value = c->refine_async;
+  else if (k == "psd_traces_batch") *value = (int)c->psd_traces_batch;
   else return VSIG_E_INVALID;
   return VSIG_OK;
 }
@@ -965,6 +971,94 @@ int vsig_psd_c64(vsig_ctx* c, const void* x, int64_t n, const float* win, int32_
   rc = vsig_psd_c64_dev(c, c->stage[0].data(), n, 1, c->stage[1].as<float>(), nperseg, hop, nfft, scale,
                         shift, c->stage[2].as<float>(), nframes);
   if (rc || (rc = stage_out(c, sxx, c->stage[2], bo))) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VSIG_OK;
+}
+
+// ---------------------------------------------------------------- spectrum traces
+int vsig_psd_traces_plan(int32_t nfft, int64_t nframes, int64_t* blocks, int64_t* frames_per_block_step,
+                         int64_t* frames_per_block) {
+  if (nfft < 1 || nframes < 1 || !blocks || !frames_per_block_step || !frames_per_block) return VSIG_E_INVALID;
+  const vsig::PsdTracesPlan p = vsig::psd_traces_plan(nfft, nframes);
+  if (p.blocks < 1) return VSIG_E_INVALID;
+  *blocks = p.blocks;
+  *frames_per_block_step = p.step;
+  *frames_per_block = p.fpb;
+  return VSIG_OK;
+}
+
+int vsig_psd_traces_c64_dev(vsig_ctx* c, const void* x, int64_t n, int64_t stride, const float* win,
+                            int32_t nperseg, int64_t hop, int32_t nfft, float scale, int32_t shift,
+                            int64_t nframes, double* mean_dev, float* max_dev, float* min_dev) {
+  if (!c || !x || !win) return fail(c, VSIG_E_INVALID, "null pointer");
+  if (!mean_dev && !max_dev && !min_dev) return fail(c, VSIG_E_INVALID, "no output asked for");
+  if (stride < 1) return fail(c, VSIG_E_INVALID, "stride must be >= 1");
+  if (nperseg < 1 || nperseg > nfft || hop < 1 || n < nperseg)
+    return fail(c, VSIG_E_INVALID, "need 1 <= nperseg <= nfft, hop >= 1, n >= nperseg");
+  if (nframes != (n - nperseg) / hop + 1) return fail(c, VSIG_E_INVALID, "nframes mismatch");
+  int rc;
+  if (vsig::psd_traces_in_lds(nfft)) {
+    // the transform kernels' epilogue reduces over the frames: one record row per block
+    const vsig::PsdTracesPlan p = vsig::psd_traces_plan(nfft, nframes);
+    if (p.blocks < 1) return fail(c, VSIG_E_INVALID, "no plan");
+    if ((rc = c->ptscratch.reserve(c, (size_t)(p.blocks * nfft) * sizeof(vsig::PsdRec)))) return rc;
+    const float2* tw;
+    bool two_level;
+    const int key = vsig::psd_traces_table(nfft, &two_level);
+    if ((rc = two_level ? get_tw2(c, key, &tw) : get_twiddles(c, key, &tw))) return rc;
+    vsig::PsdRec* rows = c->ptscratch.as<vsig::PsdRec>();
+    Timed t(c, "psd_traces");
+    HIPCHK(c, vsig::launch_psd_traces(nfft, (const float2*)x, stride, win, nperseg, hop, scale, nframes,
+                                      shift, tw, rows, c->stream));
+    HIPCHK(c, vsig::launch_psd_traces_merge(rows, p.blocks, nfft, nframes, mean_dev, max_dev, min_dev,
+                                            c->stream));
+    return VSIG_OK;
+  }
+  // every other length: vsig_psd_c64_dev's own route into a bounded batch of
+  // stored frames (256 MB, or the "psd_traces_batch" option), each batch's
+  // columns folded into the same record rows, then the same merge
+  if (!pow2_in(nfft, 64, kBigMax) && 2LL * nfft - 1 > kBigMax)
+    return fail(c, VSIG_E_UNSUPPORTED, "nfft above 2^27");
+  long long fb = (256LL << 20) / ((long long)nfft * 4);
+  if (c->psd_traces_batch > 0 && fb > c->psd_traces_batch) fb = c->psd_traces_batch;
+  if (fb < 1) fb = 1;
+  if (fb > nframes) fb = nframes;
+  const size_t rb = ((size_t)vsig::kPsdFoldRows * nfft * sizeof(vsig::PsdRec) + 255) & ~(size_t)255;
+  if ((rc = c->ptscratch.reserve(c, rb + (size_t)(fb * nfft) * sizeof(float)))) return rc;
+  vsig::PsdRec* rows = c->ptscratch.as<vsig::PsdRec>();
+  float* batch = reinterpret_cast<float*>(c->ptscratch.as<char>() + rb);
+  for (long long f0 = 0; f0 < nframes; f0 += fb) {
+    const long long nb = nframes - f0 < fb ? nframes - f0 : fb;
+    if ((rc = vsig_psd_c64_dev(c, (const float2*)x + f0 * hop * stride, (nb - 1) * hop + nperseg, stride, win,
+                               nperseg, hop, nfft, scale, shift, batch, nb)))
+      return rc;
+    HIPCHK(c, vsig::launch_psd_traces_fold(batch, nb, nfft, f0 == 0, rows, c->stream));
+  }
+  HIPCHK(c, vsig::launch_psd_traces_merge(rows, vsig::kPsdFoldRows, nfft, nframes, mean_dev, max_dev, min_dev,
+                                          c->stream));
+  return VSIG_OK;
+}
+
+int vsig_psd_traces_c64(vsig_ctx* c, const void* x, int64_t n, const float* win, int32_t nperseg,
+                        int64_t hop, int32_t nfft, float scale, int32_t shift, int64_t nframes,
+                        double* mean, float* max, float* min) {
+  if (!c || !x || !win) return fail(c, VSIG_E_INVALID, "null pointer");
+  if (!mean && !max && !min) return fail(c, VSIG_E_INVALID, "no output asked for");
+  if (n < nperseg || nperseg < 1 || hop < 1 || nfft < nperseg) return fail(c, VSIG_E_INVALID, "bad sizes");
+  const size_t bx = (size_t)n * 8, bw = (size_t)nperseg * 4, bm = (size_t)nfft * 8, bf = (size_t)nfft * 4;
+  int rc;
+  if ((rc = stage_in(c, 0, x, bx)) || (rc = stage_in(c, 1, win, bw)) || (rc = c->stage[2].reserve(c, bm + 2 * bf)))
+    return rc;
+  char* o = c->stage[2].as<char>();
+  double* dm = reinterpret_cast<double*>(o);
+  float* dx = reinterpret_cast<float*>(o + bm);
+  float* dn = reinterpret_cast<float*>(o + bm + bf);
+  rc = vsig_psd_traces_c64_dev(c, c->stage[0].data(), n, 1, c->stage[1].as<float>(), nperseg, hop, nfft, scale,
+                               shift, nframes, mean ? dm : nullptr, max ? dx : nullptr, min ? dn : nullptr);
+  if (rc) return rc;
+  if (mean) HIPCHK(c, hipMemcpyAsync(mean, dm, bm, hipMemcpyDeviceToHost, c->stream));
+  if (max) HIPCHK(c, hipMemcpyAsync(max, dx, bf, hipMemcpyDeviceToHost, c->stream));
+  if (min) HIPCHK(c, hipMemcpyAsync(min, dn, bf, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return VSIG_OK;
 }

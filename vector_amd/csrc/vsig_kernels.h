@@ -136,6 +136,31 @@ hipError_t launch_psd(int N, const float2* x, long long stride, const float* win
 int psd_plan_threads(int N);
 hipError_t launch_spectrum_prep(int N, const float2* u, int len, float gain, float2* S,
                                 const float2* tw, hipStream_t st);
+// psd_traces.hip: per-bin mean / max / min of the PSD over its frames
+// (vsig_psd_traces_c64_dev; see the file's header).  One record per bin and
+// row; its max is NaN when a NaN was folded (the record's NaN flag).
+struct PsdRec { double sum; float mx, mn; };
+// In-LDS plans (psd_traces_in_lds): `blocks` rows, block b owns the frames
+// [b fpb, (b + 1) fpb), `step` at a time.  Other lengths: the stored batches
+// are folded into kPsdFoldRows rows, frames interleaved (step 1, fpb 0).
+struct PsdTracesPlan { long long blocks, step, fpb; };
+constexpr int kPsdFoldRows = 8;
+bool psd_traces_in_lds(long long N);
+PsdTracesPlan psd_traces_plan(long long N, long long nframes);
+// The twiddle table launch_psd_traces reads for N: its plan key (plan_info's
+// convention) and whether it is the two-level table.
+int psd_traces_table(int N, bool* two_level);
+// rows: psd_traces_plan(N, nframes).blocks * N records; tw: psd_traces_table(N)'s
+hipError_t launch_psd_traces(int N, const float2* x, long long stride, const float* win, int nperseg,
+                             long long hop, float scale, long long nframes, int shift, const float2* tw,
+                             PsdRec* rows, hipStream_t st);
+// nb stored frames (frame-major float32 [nb][N]) into rows[kPsdFoldRows][N];
+// first: the rows start from the identity
+hipError_t launch_psd_traces_fold(const float* sxx, long long nb, long long N, int first, PsdRec* rows,
+                                  hipStream_t st);
+// rows[nrows][N] -> mean (sum / nframes), max, min; any output may be null
+hipError_t launch_psd_traces_merge(const PsdRec* rows, long long nrows, long long N, long long nframes,
+                                   double* mean, float* mx, float* mn, hipStream_t st);
 // Decimating FIR in the frequency domain (M = 1024, D = 2 / 4; see fir.hip).
 // mix != nullptr: the mixer above applied to every loaded sample (fused).
 hipError_t launch_fir_dec(int decim, const float2* x, long long n, long long g0, const float2* Hs,

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 import warnings
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from .windows import get_window
 
-__all__ = ["spectrum", "filter", "fir_filter", "correlate", "correlate_peak",
+__all__ = ["spectrum", "averaged_spectrum", "SpectrumTraces", "filter", "fir_filter", "correlate", "correlate_peak",
            "cross_correlate_signals", "find_correlation_peak",
            "find_packet_location_in_vector", "FirFilter", "Correlator", "peak_stats",
            "refine_status", "check_refine", "find_peaks", "find_packet_instances"]
@@ -230,6 +230,109 @@ def spectrum(x, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None, *
     if odt == np.float64:
         S = S.astype(np.float64)
     return freqs, times, S
+
+
+# ---------------------------------------------------------------------------
+# averaged_spectrum — the mean / max-hold / min-hold of spectrum()'s Sxx over
+# its frames, reduced inside the transform kernel (vsig_psd_traces_c64_dev)
+# ---------------------------------------------------------------------------
+SpectrumTraces = namedtuple("SpectrumTraces", "f mean max min nframes")
+
+_DETECTORS = ("mean", "max", "min")
+
+
+def _check_detectors(detectors):
+    detectors = (detectors,) if isinstance(detectors, str) else tuple(detectors)
+    for d in detectors:
+        if d not in _DETECTORS:
+            raise ValueError(f"unknown detector {d!r}: expected some of {_DETECTORS}")
+    if not detectors:
+        raise ValueError("no detector asked for")
+    return detectors
+
+
+def _averaged_spectrum_dev(x, window, nperseg, noverlap, nfft, fftshift, detectors, stride, nsamples):
+    """averaged_spectrum's work: (mean, max, min) device tensors in the output
+    dtype (None where not asked for), nfft and nframes; None for an empty
+    input.  Every argument error is raised before the device is touched."""
+    if _is_dev(x):
+        if x.dim() != 1:
+            raise ValueError("vector_amd works on 1-D signals")
+        n = int(nsamples if nsamples is not None else x.shape[0])
+    else:
+        if x.ndim != 1:
+            raise ValueError("vector_amd works on 1-D signals")
+        n = x.shape[0]
+    if n == 0:
+        return None
+    win, nperseg = _triage(window, nperseg, n)
+    if nfft is None:
+        nfft = nperseg
+    elif nfft < nperseg:
+        raise ValueError("nfft must be greater than or equal to nperseg.")
+    nfft = int(nfft)
+    noverlap = nperseg // 2 if noverlap is None else int(noverlap)
+    if noverlap >= nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    hop = nperseg - noverlap
+    nframes = (n - nperseg) // hop + 1
+    win32 = win.astype(np.float32)
+    scale = float(1.0 / float(np.sum(win32, dtype=np.float64)) ** 2)
+
+    ctx = _lib.get_context()
+    dev = f"cuda:{ctx.device}"
+    if _is_dev(x):
+        xd = x if x.dtype == torch.complex64 else x.to(torch.complex64)
+        if not xd.is_contiguous():
+            xd = xd.contiguous()
+        wide = x.dtype in (torch.complex128, torch.float64)
+    else:
+        xd = _device_c64(x, ctx)
+        wide = _out_real_dtype(x) == np.float64
+    wd = torch.from_numpy(win32).to(dev)
+    mean = torch.empty(nfft, dtype=torch.float64, device=dev) if "mean" in detectors else None
+    mx = torch.empty(nfft, dtype=torch.float32, device=dev) if "max" in detectors else None
+    mn = torch.empty(nfft, dtype=torch.float32, device=dev) if "min" in detectors else None
+    ctx.check(ctx.lib.vsig_psd_traces_c64_dev(
+        ctx.h, _ptr(xd), n, int(stride), _ptr(wd), nperseg, hop, nfft, scale, 1 if fftshift else 0, nframes,
+        _ptr(mean) if mean is not None else None, _ptr(mx) if mx is not None else None,
+        _ptr(mn) if mn is not None else None), "averaged_spectrum")
+    real = torch.float64 if wide else torch.float32
+    return [None if t is None else t.to(real) for t in (mean, mx, mn)], nfft, nframes
+
+
+def averaged_spectrum(x, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None, *,
+                      fftshift=False, detectors=("mean", "max", "min"), _stride=1, _nsamples=None):
+    """Per-bin traces of ``spectrum(x, fs, window, nperseg, noverlap, nfft)``'s
+    Sxx over its frames -> SpectrumTraces(f, mean, max, min, nframes), without
+    the (nfft, nframes) array ever being stored:
+
+      mean  ``Sxx.mean(axis=1)``: ``scipy.signal.welch(x, fs, window, nperseg,
+            noverlap, nfft, detrend=False, return_onesided=False,
+            scaling='spectrum', average='mean')[1]``; summed in double
+      max   ``Sxx.max(axis=1)``   a spectrum analyser's max-hold
+      min   ``Sxx.min(axis=1)``   its min-hold
+
+    detectors: the traces to compute; the others are None.  A NaN in a frame
+    makes that bin NaN in every trace, as numpy's reductions do.
+    fftshift=True returns the traces np.fft.fftshift-ed (f is not shifted, as
+    in spectrum()).  complex64 / float32 input gives float32 arrays (the
+    double mean rounded once), inputs that promote to complex128 float64.
+    numpy in -> numpy out; a CUDA tensor in -> device tensors, nothing
+    synchronised.  Argument errors are spectrum()'s; an empty input returns
+    empty arrays and nframes 0."""
+    detectors = _check_detectors(detectors)
+    dev_in = _is_dev(x)
+    if not dev_in:
+        x = np.asarray(x)
+    r = _averaged_spectrum_dev(x, window, nperseg, noverlap, nfft, fftshift, detectors, _stride, _nsamples)
+    if r is None:
+        e = np.empty((0,))
+        return SpectrumTraces(e, *(e if d in detectors else None for d in _DETECTORS), 0)
+    out, nfft, nframes = r
+    if not dev_in:
+        out = [None if t is None else t.cpu().numpy() for t in out]
+    return SpectrumTraces(np.fft.fftfreq(nfft, 1 / fs), *out, nframes)
 
 
 # ---------------------------------------------------------------------------

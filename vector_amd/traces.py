@@ -14,6 +14,11 @@ Every figure the reference draws is a spectrogram plus lines of two kinds:
       vector_analyzer/display_vectors.py:26-35   fftshifted
       vector_analyzer/mat_analyzer.py:202-215    DC removed, fftshifted, + 1e-12, minus the maximum
 
+averaged_spectrum_trace is the spectrum line for captures of any length: a
+detector (mean, max-hold, min-hold) over the frames of the block PSD
+(dsp.averaged_spectrum), where capture_spectrum is one transform of the whole
+capture and stops at 2^28 points.
+
 signal_envelope and capture_spectrum produce those lines, reduced on the
 device (trace.hip, vsig_trace_envelope_dev) to what an axis can show: with
 max_points, a min / max envelope per pixel column instead of one value per
@@ -31,9 +36,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dsp import _is_dev, _ptr
+from .dsp import _averaged_spectrum_dev, _check_detectors, _is_dev, _ptr
 
-__all__ = ["Trace", "trace_bin", "trace_envelope", "time_axis", "spectrum_axis", "signal_envelope", "capture_spectrum"]
+__all__ = ["Trace", "trace_bin", "trace_envelope", "time_axis", "spectrum_axis", "signal_envelope", "capture_spectrum",
+           "averaged_spectrum_trace"]
 
 Trace = namedtuple("Trace", "x lo hi bin argmax max")
 
@@ -307,3 +313,79 @@ def capture_spectrum(data, sample_rate, center_freq=0.0, *, scale="db", eps=0.0,
     x = spectrum_axis(n, sample_rate, center_freq, shift, lo_p, hi_p, bin_)
     lo, hi = _planes(emin, emax, dev_in)
     return Trace(x, lo, hi, bin_, argmax, mx)
+
+
+def averaged_spectrum_trace(data, sample_rate, center_freq=0.0, *, nfft=8192, window="hann", noverlap=0,
+                            detector="mean", scale="db", eps=0.0, normalize=False, max_points=None):
+    """The spectrum line of a capture of any length -> Trace(x, lo, hi, bin,
+    argmax, max): one detector of ``averaged_spectrum(data, sample_rate,
+    window, nperseg, noverlap, nfft, fftshift=True)`` -- the per-bin "mean",
+    "max" (max-hold) or "min" (min-hold) power over the capture's frames --
+    then the envelope kernel on that line.  The capture is read once and no
+    scratch of its size is needed, unlike capture_spectrum's single transform.
+
+    window: a name (frames of nfft samples, fewer for a shorter capture) or an
+      array (its length is the frame length, at most nfft); noverlap as in
+      spectrum().
+    scale: "db" is 10 * np.log10(P + eps) (P is a power), mapped by
+      vsig_db_dev on the envelope values: the map does not decrease, so the
+      envelope of the mapped line is the mapped envelope; "linear" is P.
+    normalize: subtracts the line's maximum from lo and hi; dB only.
+    x: np.fft.fftshift(np.fft.fftfreq(nfft, 1 / sample_rate)) + center_freq at
+      each column's first position (spectrum_axis).
+    max_points: at most that many columns of bin = trace_bin(nfft, max_points)
+      bins, lo / hi their minimum / maximum; bin == 1: ``lo is hi``.
+    argmax: the position in the shifted line of the first maximum; max: the
+      (mapped, normalised) value of its column in hi, a Python float.
+    lo / hi are float64 for complex128 / float64 input, else float32; numpy in
+    -> numpy out, a CUDA tensor in -> tensors.  Empty input raises ValueError."""
+    dev_in = _is_dev(data)
+    if not dev_in:
+        data = np.asarray(data)
+    _one_dim(data, dev_in)
+    if scale not in ("db", "linear"):
+        raise ValueError(f"scale must be 'db' or 'linear', got {scale!r}")
+    eps = _check_eps(eps)
+    if normalize and scale != "db":
+        raise ValueError("normalize applies to scale='db' only")
+    if not isinstance(detector, str):
+        raise ValueError(f"detector must be one name, got {detector!r}")
+    detector, = _check_detectors(detector)
+    n = int(data.shape[0])
+    if n < 1:
+        raise ValueError("averaged_spectrum_trace needs at least one sample")
+    sample_rate = float(sample_rate)
+    if not (math.isfinite(sample_rate) and sample_rate > 0):
+        raise ValueError("sample_rate must be positive and finite")
+    nfft = int(nfft)
+    if nfft < 1:
+        raise ValueError("nfft must be at least 1")
+    bin_ = trace_bin(nfft, max_points)
+    nperseg = nfft if isinstance(window, (str, tuple)) else None
+    if dev_in and not data.is_cuda:
+        data = data.to(f"cuda:{_lib.get_context().device}")
+    out, nfft, _ = _averaged_spectrum_dev(data, window, nperseg, noverlap, nfft, True, (detector,), 1, None)
+    line = out[("mean", "max", "min").index(detector)]
+    ctx = _lib.get_context(line.device.index)
+    emin, emax, info = trace_envelope(line, bin=bin_, want_min=bin_ > 1, ctx=ctx)
+    if scale == "db":
+        code = _lib.DTYPES[_CODES[line.dtype]]
+
+        def db(t):
+            o = torch.empty_like(t)
+            ctx.check(ctx.lib.vsig_db_dev(ctx.h, code, _ptr(t), int(t.numel()), eps, _ptr(o)), "db")
+            return o
+
+        emax = db(emax)
+        emin = None if emin is None else db(emin)
+    _, argmax, _, _ = _read_info(info)
+    if not 0 <= argmax < nfft:                           # a line of nothing but NaN has no maximum
+        argmax = 0
+    top = emax[argmax // bin_]
+    if normalize:
+        emax = emax - top
+        emin = None if emin is None else emin - top
+        top = emax[argmax // bin_]
+    x = spectrum_axis(nfft, sample_rate, center_freq, True, 0, nfft, bin_)
+    lo, hi = _planes(emin, emax, dev_in)
+    return Trace(x, lo, hi, bin_, argmax, float(top))
