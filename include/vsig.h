@@ -18,6 +18,8 @@
  *                     cross_correlate_signals                  utils.py:1284-1285
  *   vsig_xcorr_*      the same, streaming form with a fixed template, fused
  *                     with find_correlation_peak               utils.py:1321-1334
+ *   vsig_xcorr_bank_* K templates of one length against one stream in one pass
+ *                     (the carrier-offset search; no reference counterpart)
  *   vsig_peak_*       find_correlation_peak's |c| argmax / mean / std
  *                                                               utils.py:1321-1334
  *
@@ -63,6 +65,7 @@ extern "C" {
 typedef struct vsig_ctx vsig_ctx;
 typedef struct vsig_fir vsig_fir;
 typedef struct vsig_xcorr vsig_xcorr;
+typedef struct vsig_xcorr_bank vsig_xcorr_bank;
 
 /* Result of a |c| peak reduction (find_correlation_peak, utils.py:1321-1334).
  * index: first maximum of |c|; peak: |c[index]|; sums over every element.
@@ -142,7 +145,8 @@ int vsig_synchronize(vsig_ctx* ctx);
  *                     vsig_refine_status / vsig_synchronize wait for it.
  * and of the spectrum traces (vsig_psd_traces_c64_dev):
  *   "psd_traces_batch" 0 (default): frames per stored batch by the 256 MB rule;
- *                     > 0: at most that many (nfft outside the in-LDS plans only). */
+ *                     > 0: at most that many (nfft outside the in-LDS plans only).
+ * and of the template bank (vsig_xcorr_bank_create): "xcorr_bank_m", see there. */
 int vsig_set_option(vsig_ctx* ctx, const char* key, int value);
 int vsig_get_option(const vsig_ctx* ctx, const char* key, int* value);
 /* The hipStream_t the "refine_async" refine runs on (the context stream when
@@ -269,6 +273,39 @@ int vsig_xcorr_create(vsig_ctx* ctx, const void* tmpl, int64_t L, vsig_xcorr** o
 void vsig_xcorr_free(vsig_xcorr* xc);
 int vsig_xcorr_exec_dev(vsig_xcorr* xc, const void* s, int64_t n, int32_t mode, void* c,
                         vsig_peak_t* peak_dev);
+
+/* ---- template bank: K templates p_k of one length L (1 <= K <= 4096,
+ * 1 <= L <= 4096) against one stream in one pass (xcorr_bank.hip):
+ * c_k[o] = sum_{j<L} s[o - off + j] conj(p_k[j]), the stream transformed once
+ * per block and its spectrum multiplied with the K template spectra in turn.
+ * Serves the frequency search (one reference mixed at K offsets) and any
+ * "which of these K packets, and where" question.
+ * Record k is the UNREFINED fp32 result -- no exact re-rank runs on a bank
+ * whatever the "refine" option says: index = the first maximum of the fp32
+ * |c_k|^2, peak = its square root, the sums in double over per-wave fp32
+ * partials (what "refine" = 0 gives a single template at M <= 8192).  A NaN
+ * |c|^2 is never the maximum, and makes its own record's sums NaN.  The same
+ * call gives the same bits twice, and record / row k does not depend on the
+ * other templates of the bank.
+ * Block size M: 4096 for L <= 1024, else 8192 (measured); the
+ * option "xcorr_bank_m" (0: that rule; 4096 / 8192 / 16384 with L <= M / 2)
+ * overrides it for banks created afterwards -- a measurement hook. */
+/* tmpls: HOST complex64[K][L], row-major.  Spectra via make_spectrum, one per row. */
+int vsig_xcorr_bank_create(vsig_ctx* ctx, const void* tmpls, int32_t K, int64_t L,
+                           vsig_xcorr_bank** out);
+/* the same from a DEVICE complex64[K][L] (the rows may be freed once the call returns) */
+int vsig_xcorr_bank_create_dev(vsig_ctx* ctx, const void* tmpls_dev, int32_t K, int64_t L,
+                               vsig_xcorr_bank** out);
+void vsig_xcorr_bank_free(vsig_xcorr_bank* bank);
+/* mode VALID / FULL as vsig_xcorr_exec_dev.  c: device complex64[K][nout] or NULL.
+ * peaks_dev: device vsig_peak_t[K] (required).  Enqueued on the context stream, no sync. */
+int vsig_xcorr_bank_exec_dev(vsig_xcorr_bank* bank, const void* s, int64_t n, int32_t mode, void* c,
+                             vsig_peak_t* peaks_dev);
+/* the geometry the exec will use, for tests and tools: M, hop (outputs per block),
+ * nblocks = ceil(nout / hop), and the launched (persistent) grid: a launched block
+ * walks blocks b, b + grid, ... */
+int vsig_xcorr_bank_plan(const vsig_xcorr_bank* bank, int64_t n, int32_t mode, int32_t* M,
+                         int64_t* hop, int64_t* nblocks, int64_t* grid);
 
 /* ---- general correlation, np.correlate(a, v, mode) semantics for any length
  * order (cross_correlate_signals, utils.py:1279-1285): output length full

@@ -8,9 +8,11 @@ a HIP device every call raises ``VsigUnavailable``.
 from ._lib import (RefineFault, VsigError, VsigInvalid, VsigUnavailable, get_context,  # noqa: F401
                    load_library)
 from . import dsp  # noqa: F401
-from .dsp import (Correlator, FirFilter, SpectrumTraces, averaged_spectrum, correlate, correlate_peak,  # noqa: F401
+from .dsp import (Correlator, CorrelatorBank, FirFilter, FrequencySearch, SpectrumTraces,  # noqa: F401
+                  averaged_spectrum, correlate, correlate_peak,
                   cross_correlate_signals, filter, find_correlation_peak,
-                  find_packet_instances, find_packet_location_in_vector, find_peaks, fir_filter,
+                  find_packet_instances, find_packet_location_in_vector,
+                  find_packet_location_with_offset, find_peaks, fir_filter, frequency_search,
                   peak_stats, spectrum)
 from .spectrogram import create_spectrogram, spectrogram_params  # noqa: F401
 from .channelizer import Channelizer, filter_channel, pfb_channelize  # noqa: F401

@@ -93,6 +93,7 @@ struct vsig_ctx {
   DevBuf tscratch;                       // trace.hip per-block / per-chunk / per-column records
   DevBuf ptscratch;                      // psd_traces.hip record rows (+ the fold route's frame batch)
   long long psd_traces_batch = 0;        // fold route: frames per batch at most (0: the 256 MB rule)
+  int xcorr_bank_m = 0;                  // template bank block size (0: by template length)
   PeakPartial* parts() const { return partials.as<PeakPartial>(); }
   // the first-level buffer of a two-level finalize, right after the partials,
   // then the fused finalize's block counters (zero between launches)
@@ -159,6 +160,21 @@ struct vsig_xcorr {
   explicit vsig_xcorr(vsig_ctx* c) : ctx(c) {}
   // the stream may still use the spectra: wait, then the members free them
   ~vsig_xcorr() { (void)hipStreamSynchronize(ctx->stream); }
+};
+
+// A bank of K templates of one length L <= kBankMaxL: the K spectra of M
+// points in one table (row k at Ps + k M).
+constexpr long long kBankMaxL = 4096;
+constexpr int kBankMaxK = 4096;
+struct vsig_xcorr_bank {
+  vsig_ctx* ctx;
+  int K = 0;
+  long long L = 0;
+  int M = 0;
+  DevBuf Ps;
+  explicit vsig_xcorr_bank(vsig_ctx* c) : ctx(c) {}
+  // the stream may still use the spectra: wait, then the member frees them
+  ~vsig_xcorr_bank() { (void)hipStreamSynchronize(ctx->stream); }
 };
 
 namespace {
@@ -749,6 +765,10 @@ int vsig_set_option(vsig_ctx* c, const char* key, int value) {
   } else if (k == "psd_traces_batch") {
     if (value < 0) return fail(c, VSIG_E_INVALID, "psd_traces_batch must be >= 0");
     c->psd_traces_batch = value;
+  } else if (k == "xcorr_bank_m") {
+    if (value != 0 && value != 4096 && value != 8192 && value != 16384)
+      return fail(c, VSIG_E_INVALID, "xcorr_bank_m must be 0, 4096, 8192 or 16384");
+    c->xcorr_bank_m = value;
   } else if (k == "refine_async") {
     vsig_ctx::RefineAsync& ra = c->ra;
     if (value && !ra.stream) {
@@ -779,6 +799,7 @@ int vsig_get_option(const vsig_ctx* c, const char* key, int* value) {
   else if (k == "blas_threads") *value = c->blas_threads;
   else if (k == "refine_async") *value = c->refine_async;
   else if (k == "psd_traces_batch") *value = (int)c->psd_traces_batch;
+  else if (k == "xcorr_bank_m") *value = c->xcorr_bank_m;
   else return VSIG_E_INVALID;
   return VSIG_OK;
 }
@@ -1346,6 +1367,128 @@ int vsig_xcorr_exec_dev(vsig_xcorr* x, const void* s, int64_t n, int32_t mode, v
   const RefineOperands op{s, n, x->tmpl.data(), x->L, 0, (x->L - 1) - off};
   return xcorr_run(x, (const float2*)s, n, off, nout, cout ? 1 : 0, (float2*)cout, peak_dev, &op,
                    nullptr, true);
+}
+
+// ---------------------------------------------------------------- template bank
+// Block size of a bank of templates of L samples: 4096 up to L = 1024, 8192
+// above (hop 4097 at L = 4096; measured against M = 16384).
+static int os_size_bank(long long L) { return L <= 1024 ? 4096 : 8192; }
+
+// The partials of one launch are held to this many records (256 MB): a bank
+// whose K groups need more runs as several launches over runs of templates.
+constexpr long long kBankPartialsCap = 1LL << 23;
+
+struct BankGeom {
+  long long off, nout, hop, nblocks, grid, npk;   // npk: partials per template
+  int waves;
+};
+
+static int bank_geom(const vsig_xcorr_bank* x, long long n, int mode, BankGeom* g) {
+  vsig_ctx* c = x->ctx;
+  if (mode == VSIG_MODE_VALID) { g->off = 0; g->nout = n - x->L + 1; }
+  else if (mode == VSIG_MODE_FULL) { g->off = x->L - 1; g->nout = n + x->L - 1; }
+  else return fail(c, VSIG_E_INVALID, "the template bank supports VALID and FULL");
+  if (n < 1 || g->nout < 1) return fail(c, VSIG_E_INVALID, "stream shorter than the templates");
+  g->hop = (long long)x->M - x->L + 1;
+  g->nblocks = (g->nout + g->hop - 1) / g->hop;
+  if (vsig::xcorr_bank_geom(x->M, g->nblocks, &g->waves, &g->grid) != hipSuccess)
+    return fail(c, VSIG_E_UNSUPPORTED, "template bank block size");
+  g->npk = g->nblocks * g->waves;
+  return VSIG_OK;
+}
+
+// td: DEVICE complex64[K][L]
+static int bank_create(vsig_ctx* c, const float2* td, int K, long long L, vsig_xcorr_bank** out) {
+  std::unique_ptr<vsig_xcorr_bank> x(new vsig_xcorr_bank(c));
+  x->K = K;
+  x->L = L;
+  x->M = os_size_bank(L);
+  if (c->xcorr_bank_m) {
+    if (2 * L > c->xcorr_bank_m)
+      return fail(c, VSIG_E_INVALID, "xcorr_bank_m: the templates are longer than half the block");
+    x->M = c->xcorr_bank_m;
+  }
+  const float2* tw;
+  int rc = get_twiddles(c, x->M, &tw);
+  if (rc) return rc;
+  HIPCHK(c, x->Ps.alloc((size_t)K * x->M * sizeof(float2)));
+  for (int k = 0; k < K; ++k)      // make_spectrum's launch, row k into the table
+    HIPCHK(c, vsig::launch_spectrum_prep(x->M, td + (long long)k * L, (int)L, 1.0f / (float)x->M,
+                                         x->Ps.as<float2>() + (long long)k * x->M, tw, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // the caller's templates are free to go
+  *out = x.release();
+  return VSIG_OK;
+}
+
+static int bank_check(vsig_ctx* c, const void* tmpls, int32_t K, int64_t L, vsig_xcorr_bank** out) {
+  if (!c || !tmpls || !out) return fail(c, VSIG_E_INVALID, "null pointer");
+  *out = nullptr;
+  if (K < 1 || K > kBankMaxK)
+    return fail(c, VSIG_E_INVALID, "template bank: K must be in [1, " + std::to_string(kBankMaxK) + "]");
+  if (L < 1) return fail(c, VSIG_E_INVALID, "template length must be >= 1");
+  if (L > kBankMaxL)
+    return fail(c, VSIG_E_UNSUPPORTED,
+                "template bank: templates of at most " + std::to_string(kBankMaxL) + " samples");
+  return VSIG_OK;
+}
+
+int vsig_xcorr_bank_create(vsig_ctx* c, const void* tmpls, int32_t K, int64_t L, vsig_xcorr_bank** out) {
+  int rc = bank_check(c, tmpls, K, L, out);
+  if (rc) return rc;
+  DevBuf td;      // freed after bank_create's synchronise
+  const size_t bytes = (size_t)K * (size_t)L * sizeof(float2);
+  HIPCHK(c, td.alloc(bytes));
+  HIPCHK(c, hipMemcpyAsync(td.data(), tmpls, bytes, hipMemcpyHostToDevice, c->stream));
+  rc = bank_create(c, td.as<float2>(), K, L, out);
+  (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+
+int vsig_xcorr_bank_create_dev(vsig_ctx* c, const void* tmpls_dev, int32_t K, int64_t L,
+                               vsig_xcorr_bank** out) {
+  const int rc = bank_check(c, tmpls_dev, K, L, out);
+  if (rc) return rc;
+  return bank_create(c, (const float2*)tmpls_dev, K, L, out);
+}
+
+void vsig_xcorr_bank_free(vsig_xcorr_bank* x) { delete x; }
+
+int vsig_xcorr_bank_plan(const vsig_xcorr_bank* x, int64_t n, int32_t mode, int32_t* M, int64_t* hop,
+                         int64_t* nblocks, int64_t* grid) {
+  if (!x) return VSIG_E_INVALID;
+  if (!M || !hop || !nblocks || !grid) return fail(x->ctx, VSIG_E_INVALID, "null pointer");
+  BankGeom g;
+  const int rc = bank_geom(x, n, mode, &g);
+  if (rc) return rc;
+  *M = x->M; *hop = g.hop; *nblocks = g.nblocks; *grid = g.grid;
+  return VSIG_OK;
+}
+
+int vsig_xcorr_bank_exec_dev(vsig_xcorr_bank* x, const void* s, int64_t n, int32_t mode, void* cout,
+                             vsig_peak_t* peaks_dev) {
+  if (!x) return VSIG_E_INVALID;
+  vsig_ctx* c = x->ctx;
+  if (!s || !peaks_dev) return fail(c, VSIG_E_INVALID, "null pointer");
+  BankGeom g;
+  int rc = bank_geom(x, n, mode, &g);
+  if (rc) return rc;
+  // templates per launch (the partials' cap); ensure_partials joins a pending
+  // asynchronous refine of this context before its partials are overwritten
+  long long kc = kBankPartialsCap / g.npk;
+  kc = kc < 1 ? 1 : kc > x->K ? x->K : kc;
+  if ((rc = ensure_partials(c, kc * g.npk))) return rc;
+  const float2* tw;
+  if ((rc = get_twiddles(c, x->M, &tw))) return rc;
+  Timed t(c, "xcorr_bank");
+  for (long long k0 = 0; k0 < x->K; k0 += kc) {
+    const int kn = (int)(x->K - k0 < kc ? x->K - k0 : kc);
+    float2* ck = cout ? (float2*)cout + k0 * g.nout : nullptr;
+    HIPCHK(c, vsig::launch_xcorr_bank(x->M, (const float2*)s, n, x->Ps.as<float2>() + k0 * x->M, kn,
+                                      g.off, g.nout, g.hop, ck, c->parts(), tw, c->stream));
+    HIPCHK(c, vsig::launch_bank_finalize(c->parts(), kn, g.npk,
+                                         reinterpret_cast<PeakPartial*>(peaks_dev) + k0, c->stream));
+  }
+  return VSIG_OK;
 }
 
 // np.correlate(a, v, mode): the shorter operand is the template; with

@@ -190,6 +190,17 @@ int xcorr_lane_keys(int M);
 // Outputs of wave w of block b of the correlator for M (the refine pass's
 // items): ob + wstep w + l + 64 (q % rsub) + stride (q / rsub), l < 64, q < Q.
 hipError_t xcorr_geom(int M, int* waves, int* Q, int* stride, int* plan, int* wstep, int* rsub);
+// xcorr_bank.hip: K templates of one length against one stream, M in {4096,
+// 8192, 16384}.  Ps: K spectra of M points; c: K rows of nout (may be null);
+// partials[(k nblocks + b) waves + wave], nblocks = ceil(nout / hop), with
+// waves and the launched (persistent) grid from xcorr_bank_geom.
+hipError_t xcorr_bank_geom(int M, long long nblocks, int* waves, long long* grid);
+hipError_t launch_xcorr_bank(int M, const float2* s, long long n, const float2* Ps, int K,
+                             long long off, long long nout, long long hop, float2* c,
+                             PeakPartial* partials, const float2* tw, hipStream_t st);
+// out[k] = the record (max |c|, first index, sums) of group k of nparts partials
+hipError_t launch_bank_finalize(const PeakPartial* parts, int K, long long nparts, PeakPartial* out,
+                                hipStream_t st);
 #ifdef VSIG_TUNING
 // Tuning micro-benchmarks: iters FFTs per frame, frames blocks (key: plan key).
 hipError_t launch_fft_bench(int key, float2* io, int frames, int iters, const float2* tw, int twl,

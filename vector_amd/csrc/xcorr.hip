@@ -6,7 +6,7 @@
 //   M = 4096 / 8192 (templates up to 1024 / 2048): xcorr_os_kernel, one frame
 //     per block, persistent with the next segment prefetched.
 // Both use register twiddle anchors (no global loads inside a transform).
-#include "os_common.hpp"
+#include "xcorr_epilogue.hpp"
 
 namespace vsig {
 
@@ -22,54 +22,6 @@ namespace vsig {
 //   b*hop + 64 w + l + TF q,   l < 64, q < Q   (Q = E, or 2 E for the half
 // kernel), which refine.hip uses to revisit a wave's outputs (xcorr_geom).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void put_c(float2* p, float2 v, bool accum) {
-  *p = accum ? cadd(*p, v) : v;
-}
-
-template <class P>
-__device__ __forceinline__ void xcorr_epilogue(const float2* v, long long b, long long hop,
-                                               long long nout, float2* __restrict__ c,
-                                               int store_mode, PeakPartial* partials, int t) {
-  const long long ob = b * hop;                         // block's first output
-  const long long rem = nout - ob;
-  const int lim = rem < hop ? (int)rem : (int)hop;
-  const bool rev = store_mode & 4;
-  const bool accum = store_mode & 8;
-  const int smode = store_mode & 3;
-  if (smode == 1) {
-#pragma unroll
-    for (int e = 0; e < P::E; ++e) {
-      const int i = out_index<P>(t, e);
-      if (i < lim) put_c(c + ob + (unsigned)i, cconj(v[e]), accum);
-    }
-  } else if (smode == 2) {
-#pragma unroll
-    for (int e = 0; e < P::E; ++e) {
-      const int i = out_index<P>(t, e);
-      if (i < lim) put_c(c + (nout - 1 - ob) - i, v[e], accum);
-    }
-  }
-  if (!partials) return;
-  // branch-free peak / sums.  A thread's output indices rise with e, so a
-  // strict '>' keeps the first maximum; in the reversed index space (rev)
-  // '>=' keeps the last raw index, i.e. the first reversed one.
-  float m = -1.f, s1 = 0.f, s2 = 0.f;
-  int mi = 0;
-#pragma unroll
-  for (int e = 0; e < P::E; ++e) {
-    const int i = out_index<P>(t, e);
-    const bool ok = i < lim;
-    const float a2r = v[e].x * v[e].x + v[e].y * v[e].y;
-    const float a2 = ok ? a2r : -1.f;
-    const bool take = (a2 > m) | (rev & (a2 == m) & ok);
-    m = take ? a2 : m;
-    mi = take ? i : mi;
-    s1 += ok ? __builtin_amdgcn_sqrtf(a2r) : 0.f;   // v_sqrt_f32 (1 ulp), not the IEEE expansion
-    s2 += ok ? a2r : 0.f;
-  }
-  wave_partial_f(m, mi, s1, s2, rev, ob, nout, partials + b * (P::TF / 64) + (t >> 6));
-}
-
 // Persistent: a block walks blocks b, b + grid, ...; the next segment is
 // loaded behind the (L2-resident) template-spectrum loads, so it lands while
 // the inverse FFT runs (vmcnt retires in issue order).

@@ -32,7 +32,8 @@ from .windows import get_window
 __all__ = ["spectrum", "averaged_spectrum", "SpectrumTraces", "filter", "fir_filter", "correlate", "correlate_peak",
            "cross_correlate_signals", "find_correlation_peak",
            "find_packet_location_in_vector", "FirFilter", "Correlator", "peak_stats",
-           "refine_status", "check_refine", "find_peaks", "find_packet_instances"]
+           "refine_status", "check_refine", "find_peaks", "find_packet_instances",
+           "CorrelatorBank", "FrequencySearch", "frequency_search", "find_packet_location_with_offset"]
 
 PEAK_BYTES = 32  # sizeof(vsig_peak_t)
 
@@ -724,6 +725,223 @@ class Correlator:
 
 
 # ---------------------------------------------------------------------------
+# template bank — K templates against one stream in one pass; the carrier
+# offset search built on it
+# ---------------------------------------------------------------------------
+BANK_MAX_TEMPLATES = 4096      # vsig_xcorr_bank_create: K and L limits
+BANK_MAX_LENGTH = 4096
+
+
+def _bank_templates(templates):
+    """(rows, K, L, on_device) of a (K, L) template set, checked on the host."""
+    if _is_dev(templates):
+        t = templates
+        shape, dev = tuple(t.shape), t.is_cuda
+    else:
+        t = np.asarray(templates)
+        shape, dev = t.shape, False
+    if len(shape) != 2:
+        raise ValueError(f"CorrelatorBank: templates must be a (K, L) array, got shape {tuple(shape)}")
+    K, L = int(shape[0]), int(shape[1])
+    if K < 1 or L < 1:
+        raise ValueError(f"CorrelatorBank: empty template set {tuple(shape)}")
+    if K > BANK_MAX_TEMPLATES:
+        raise ValueError(f"CorrelatorBank: {K} templates, at most {BANK_MAX_TEMPLATES}")
+    if L > BANK_MAX_LENGTH:
+        raise NotImplementedError(f"CorrelatorBank: templates of {L} samples, at most {BANK_MAX_LENGTH}")
+    return t, K, L, dev
+
+
+class CorrelatorBank:
+    """K templates of one length L (K, L <= 4096) correlated against one
+    device-resident stream in one pass: the stream's transform runs once per
+    block and its spectrum meets the K template spectra in registers
+    (vsig_xcorr_bank_*).  ``templates``: a (K, L) complex array-like, or a CUDA
+    complex64 tensor (used where it is).  Record k is the unrefined fp32
+    result: the first maximum of the fp32 |c_k|^2, its square root, and the
+    sums of |c_k| and |c_k|^2 -- no exact re-rank runs on a bank."""
+
+    def __init__(self, templates, device: int | None = None):
+        t, self.K, self.L, dev = _bank_templates(templates)
+        self.h = None
+        self.ctx = _lib.get_context(device)
+        h = C.c_void_p()
+        lib = self.ctx.lib
+        if dev:
+            if t.device.index != self.ctx.device:
+                raise ValueError(f"templates: on {t.device}, expected cuda:{self.ctx.device}")
+            t = t.to(torch.complex64).contiguous()
+            self.ctx.check(lib.vsig_xcorr_bank_create_dev(self.ctx.h, _ptr(t), self.K, self.L, C.byref(h)),
+                           "vsig_xcorr_bank_create_dev")
+        else:
+            a = t.numpy() if _is_dev(t) else t
+            a = np.ascontiguousarray(a, dtype=np.complex64)
+            self.ctx.check(lib.vsig_xcorr_bank_create(self.ctx.h, a.ctypes.data_as(C.c_void_p), self.K,
+                                                      self.L, C.byref(h)), "vsig_xcorr_bank_create")
+        self.h = h
+
+    def out_len(self, n: int, mode="valid") -> int:
+        if mode not in ("valid", "full"):
+            raise ValueError("CorrelatorBank supports mode 'valid' and 'full'")
+        return n - self.L + 1 if mode == "valid" else n + self.L - 1
+
+    def plan(self, n: int, mode="valid"):
+        """(M, hop, nblocks, grid) of a call on n samples (vsig_xcorr_bank_plan)."""
+        self.out_len(n, mode)
+        M, hop, nb, grid = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        self.ctx.check(self.ctx.lib.vsig_xcorr_bank_plan(self.h, int(n), _lib.MODES[mode], C.byref(M),
+                                                         C.byref(hop), C.byref(nb), C.byref(grid)),
+                       "vsig_xcorr_bank_plan")
+        return int(M.value), int(hop.value), int(nb.value), int(grid.value)
+
+    def __call__(self, s: torch.Tensor, mode="valid", out: torch.Tensor | None = None,
+                 peaks: torch.Tensor | None = None):
+        """Enqueue; returns (out or None, peaks): out a (K, nout) complex64
+        device tensor, peaks a (K, 4) float64 device tensor of K vsig_peak_t
+        records (read_peaks)."""
+        self.ctx.bind_stream()
+        _check_dev(s, 1, torch.complex64, "correlator stream", self.ctx.device)
+        if s.dim() != 1:
+            raise ValueError("correlator stream: expected a 1-D tensor")
+        ns = int(s.shape[0])
+        nout = self.out_len(ns, mode)
+        if nout < 1:
+            raise ValueError("stream shorter than the templates")
+        if out is not None:
+            _check_dev(out, self.K * nout, torch.complex64, "correlator output", self.ctx.device)
+        if peaks is None:
+            peaks = torch.empty((self.K, PEAK_BYTES // 8), dtype=torch.float64, device=s.device)
+        _check_dev(peaks, 4 * self.K, torch.float64, "peak records", self.ctx.device)
+        self.ctx.check(self.ctx.lib.vsig_xcorr_bank_exec_dev(
+            self.h, _ptr(s), ns, _lib.MODES[mode], _ptr(out) if out is not None else None,
+            _ptr(peaks)), "xcorr bank")
+        return out, peaks
+
+    @staticmethod
+    def read_peaks(peaks: torch.Tensor):
+        """Host arrays (peak[K], index[K], sum_abs[K], sum_abs2[K]) of the records."""
+        h = peaks.detach().cpu().contiguous().reshape(-1, PEAK_BYTES // 8)
+        raw = h.numpy()
+        idx = h.view(torch.int64).numpy()[:, 1].copy()
+        return raw[:, 0].copy(), idx, raw[:, 2].copy(), raw[:, 3].copy()
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.ctx.lib.vsig_xcorr_bank_free(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+FrequencySearch = namedtuple("FrequencySearch", ["offset_hz", "lag", "peak", "confidence", "offsets",
+                                                 "lags", "peaks", "confidences"])
+
+
+def _search_grid(offsets, max_offset, step, sample_rate, Lt):
+    """The hypotheses in Hz, checked on the host."""
+    if (offsets is None) == (max_offset is None):
+        raise ValueError("frequency_search: give exactly one of offsets and max_offset")
+    if offsets is not None:
+        if step is not None:
+            raise ValueError("frequency_search: step goes with max_offset, not with offsets")
+        grid = np.array(offsets, dtype=np.float64)
+        if grid.ndim != 1:
+            raise ValueError("frequency_search: offsets must be a 1-D array of Hz")
+    else:
+        max_offset = float(max_offset)
+        if not np.isfinite(max_offset) or max_offset < 0:
+            raise ValueError("frequency_search: max_offset must be finite and >= 0")
+        step = sample_rate / (2.0 * Lt) if step is None else float(step)
+        if not np.isfinite(step) or step <= 0:
+            raise ValueError("frequency_search: step must be finite and > 0")
+        m = int(np.ceil(max_offset / step))
+        if 2 * m + 1 > BANK_MAX_TEMPLATES:
+            raise ValueError(f"frequency_search: {2 * m + 1} hypotheses, at most {BANK_MAX_TEMPLATES} "
+                             "(a coarser step, or several searches)")
+        grid = np.arange(-m, m + 1) * step
+    if grid.size == 0:
+        raise ValueError("frequency_search: empty offset grid")
+    if grid.size > BANK_MAX_TEMPLATES:
+        raise ValueError(f"frequency_search: {grid.size} hypotheses, at most {BANK_MAX_TEMPLATES}")
+    if not np.all(np.isfinite(grid)):
+        raise ValueError("frequency_search: offsets must be finite")
+    return grid
+
+
+def _len1d(x, what):
+    shape = tuple(x.shape) if _is_dev(x) else np.shape(x)
+    if len(shape) != 1:
+        raise ValueError(f"{what}: vector_amd works on 1-D signals")
+    return int(shape[0])
+
+
+def frequency_search(vector, reference, sample_rate, offsets=None, *, max_offset=None, step=None,
+                     mode="valid", threshold_ratio=0.5, max_template=4096):
+    """Where ``reference`` sits in ``vector`` and at which carrier offset:
+    hypothesis k is ``apply_frequency_shift(reference[:Lt], offsets[k],
+    sample_rate)`` (built on the device by the same mixer), all K correlated
+    against the vector in one pass (CorrelatorBank), so a packet that
+    build_vector placed with ``freq_shift = f`` is found at offset ``+f``.
+
+    Give exactly one of ``offsets`` (1-D, Hz, finite, 1 .. 4096 entries) and
+    ``max_offset``; with ``max_offset`` the grid is ``np.arange(-m, m + 1) *
+    step``, ``m = ceil(max_offset / step)``, and ``step`` defaults to
+    ``sample_rate / (2 * Lt)`` -- a worst-case mismatch of a quarter cycle over
+    the template, which keeps sinc(1/4) = 0.90 of the peak.
+
+    Only the first ``Lt = min(len(reference), max_template)`` samples of the
+    reference are correlated (``max_template`` <= 4096, the bank's limit); the
+    lag is still the start of the reference.  Returns a FrequencySearch:
+    the winner (first maximum of ``peaks``) as ``offset_hz, lag, peak,
+    confidence`` and every hypothesis as ``offsets, lags, peaks, confidences``.
+    ``lag`` is correlate_peak(reference[:Lt], vector, mode)'s; ``confidence``
+    is find_correlation_peak's z-score formula on the fused fp32 sums of each
+    hypothesis.  The records are the bank's unrefined fp32 results; run
+    correlate_peak on the vector mixed by ``-offset_hz`` for numpy's own
+    (find_packet_location_with_offset does)."""
+    if mode not in ("valid", "full"):
+        raise ValueError("frequency_search supports mode 'valid' and 'full'")
+    sample_rate = float(sample_rate)
+    if not np.isfinite(sample_rate) or sample_rate <= 0:
+        raise ValueError("frequency_search: sample_rate must be finite and > 0")
+    max_template = int(max_template)
+    if not 1 <= max_template <= BANK_MAX_LENGTH:
+        raise ValueError(f"frequency_search: max_template must be in [1, {BANK_MAX_LENGTH}]")
+    nref, nvec = _len1d(reference, "reference"), _len1d(vector, "vector")
+    if nref < 1:
+        raise ValueError("frequency_search: empty reference")
+    Lt = min(nref, max_template)
+    grid = _search_grid(offsets, max_offset, step, sample_rate, Lt)
+    nout = nvec - Lt + 1 if mode == "valid" else nvec + Lt - 1
+    if nvec < 1 or nout < 1:
+        raise ValueError("frequency_search: vector shorter than the reference")
+    ctx = _lib.get_context()
+    ctx.bind_stream()
+    ref = _device_c64(reference, ctx)[:Lt].contiguous()
+    K = int(grid.size)
+    rows = torch.empty((K, Lt), dtype=torch.complex64, device=ref.device)
+    for k, f in enumerate(grid):
+        if f == 0:                       # apply_frequency_shift returns the signal itself
+            rows[k].copy_(ref)
+            continue
+        w = (2j * np.pi * f).imag        # the imaginary part numpy multiplies t by
+        ctx.check(ctx.lib.vsig_mix_c64_dev(ctx.h, _ptr(ref), Lt, float(w), sample_rate, 0,
+                                           C.c_void_p(rows[k].data_ptr())), "mix")
+    bank = CorrelatorBank(rows, ctx.device)
+    _, pk = bank(_device_c64(vector, ctx), mode)
+    peaks, idx, s1, s2 = bank.read_peaks(pk)
+    lags = idx - (Lt - 1) if mode == "full" else idx
+    confs = np.empty(K, dtype=np.float64)
+    for k in range(K):
+        mean, std, _ = _fused_stats(peaks[k], s1[k], s2[k], nout)
+        confs[k] = _confidence_np(peaks[k], mean, std, threshold_ratio)
+    best = int(np.argmax(np.where(np.isnan(peaks), -np.inf, peaks)))
+    return FrequencySearch(np.float64(grid[best]), np.int64(lags[best]), np.float64(peaks[best]),
+                           np.float64(confs[best]), grid, lags.astype(np.int64), peaks, confs)
+
+
+# ---------------------------------------------------------------------------
 # peak list — every instance, where find_correlation_peak stops at one argmax
 # ---------------------------------------------------------------------------
 def _check_peaks_args(threshold, min_distance, max_peaks):
@@ -859,3 +1077,28 @@ def find_packet_location_in_vector(vector, packet_signal, reference_segment,
     vlag, _, vconf = correlate_peak(reference_segment, vector[s0:s1], "full", correlation_threshold)
     plag, _, pconf = correlate_peak(reference_segment, packet_signal, "full", correlation_threshold)
     return s0 + vlag - plag, 0, min(vconf, pconf)
+
+
+def find_packet_location_with_offset(vector, packet_signal, reference_segment, sample_rate, max_offset,
+                                     step=None, search_window=None, correlation_threshold=0.5):
+    """find_packet_location_in_vector for a vector whose carrier is off by an
+    unknown offset of at most ``max_offset`` Hz (a reference cut from another
+    capture): frequency_search of the reference over the search window, then
+    the window mixed by ``-offset_hz`` once (apply_frequency_shift) and handed
+    to find_packet_location_in_vector -- the location and confidence are that
+    function's refined, numpy-exact ones.  Returns (vector_location,
+    offset_hz, confidence)."""
+    from .vectors import apply_frequency_shift
+    n = _len1d(vector, "vector")
+    if search_window is None:
+        s0, s1 = 0, n
+    else:
+        s0, s1 = search_window
+        s0, s1 = max(0, s0), min(n, s1)
+    region = vector[s0:s1]
+    fs = frequency_search(region, reference_segment, sample_rate, max_offset=max_offset, step=step,
+                          mode="full", threshold_ratio=correlation_threshold)
+    region = apply_frequency_shift(region, -float(fs.offset_hz), sample_rate)
+    loc, _, conf = find_packet_location_in_vector(region, packet_signal, reference_segment, None,
+                                                  correlation_threshold)
+    return s0 + loc, fs.offset_hz, conf
