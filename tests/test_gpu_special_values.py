@@ -563,3 +563,182 @@ def test_c4_stored_correlation_contains_a_non_finite_sample(gpu):
         assert not (covered & fin).any(), (v, np.flatnonzero(covered & fin)[:8])
         same = sv.same_bits(c, clean).reshape(-1, 2).all(axis=1)
         assert same[far].all(), (v, np.flatnonzero(far & ~same)[:8])
+
+
+# =========================================================================== D
+# An unknown dtype code at every *_dev entry point that takes one: the status
+# vsig_api.hip gives it (most refuse it themselves; vsig_db_dev and the two
+# abs entry points hand it to their launcher, whose hipErrorInvalidValue comes
+# back as VSIG_E_HIP), and the context goes on working.
+E_INVALID, E_HIP, E_UNSUPPORTED = -1, -2, -4
+_EPS32, _EPS64 = float(np.finfo(np.float32).eps), float(np.finfo(np.float64).eps)
+_DX = (np.random.default_rng(7).standard_normal(16) + 1j * np.random.default_rng(8).standard_normal(16))
+_DV = _DX[3:7].copy()
+_DR = np.ascontiguousarray(_DX.real)
+_DROWS = np.array([3, 17, 40, 64, 99, 100, 128, 150, 177, 200, 201, 222, 240, 250, 254, 255])
+_DMAG = np.abs(_DX)
+# every FFT-based entry point below is one or two 16-point complex64
+# transforms of _DX: an output's error is at most n eps32 sum|x| a transform
+# (n terms, each off by at most n / 2 roundings), doubled for margin
+_FFT_TOL = 4 * 16 * _EPS32 * float(_DMAG.sum())
+
+
+def _zeros(n, dt):
+    return torch.zeros(n, dtype=dt, device="cuda")
+
+
+def _d_peak(ctx, code):
+    x, pk = _dev(_DX), _zeros(4, torch.float64)
+    rc = ctx.lib.vsig_peak_dev(ctx.h, code, _ptr(x), 16, _ptr(pk))
+    return rc, lambda: (pk[0].item() == _DMAG.max() and pk.view(torch.int64)[1].item() == _DMAG.argmax())
+
+
+def _d_peaks(ctx, code):
+    x, out, info = _dev(_DX), _zeros(8, torch.int64), _zeros(4, torch.int64)
+    rc = ctx.lib.vsig_peaks_dev(ctx.h, code, _ptr(x), 16, 0.0, 0, 16, _ptr(out), 4, _ptr(info))
+    return rc, lambda: (info[:2].tolist() == [1, _DMAG.argmax()] and out[0].item() == _DMAG.argmax()
+                        and out.view(torch.float64)[1].item() == _DMAG.max())
+
+
+def _d_trace(ctx, code):
+    x, lo, hi, info = _dev(_DX), _zeros(4, torch.float64), _zeros(4, torch.float64), _zeros(4, torch.int64)
+    rc = ctx.lib.vsig_trace_envelope_dev(ctx.h, code, _ptr(x), 16, 0, 0, 16, 4, _lib.TRACE_ABS, 0.0, _ptr(lo),
+                                         _ptr(hi), _ptr(info))
+    m = _DMAG.reshape(4, 4)
+    return rc, lambda: (np.array_equal(lo.cpu().numpy(), m.min(1)) and np.array_equal(hi.cpu().numpy(), m.max(1))
+                        and info[:2].tolist() == [_DMAG.argmin(), _DMAG.argmax()])
+
+
+def _d_abs_stats(ctx, code):
+    x, st = _dev(_DX), _zeros(2, torch.float64)
+    rc = ctx.lib.vsig_abs_stats_dev(ctx.h, code, _ptr(x), 16, _ptr(st))
+    # 16 magnitudes of at most 4 roundings each, summed: 64 eps64 max|a| covers mean and std
+    return rc, lambda: np.allclose(st.cpu().numpy(), [_DMAG.mean(), _DMAG.std()], rtol=0,
+                                   atol=64 * _EPS64 * _DMAG.max())
+
+
+def _d_select(ctx, code):
+    x, ranks, vals = _dev(_DR), (C.c_int64 * 3)(0, 8, 15), (C.c_double * 3)()
+    rc = ctx.lib.vsig_select_dev(ctx.h, code, _ptr(x), 16, ranks, 3, vals)
+    return rc, lambda: list(vals) == np.sort(np.abs(_DR))[[0, 8, 15]].tolist()
+
+
+def _d_threshold(ctx, code):
+    x, thr = _dev(_DR), float(np.median(np.abs(_DR)))
+    cnt, first, last, mx = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+    rc = ctx.lib.vsig_threshold_dev(ctx.h, code, _ptr(x), 16, thr, C.byref(cnt), C.byref(first), C.byref(last),
+                                    C.byref(mx))
+    hit = np.flatnonzero(np.abs(_DR) >= thr)
+    return rc, lambda: (cnt.value, first.value, last.value, mx.value) == (len(hit), hit[0], hit[-1],
+                                                                           np.abs(_DR).max())
+
+
+def _d_boxcar(ctx, code):
+    x, sm = _dev(_DX), _zeros(16, torch.float64)
+    rc = ctx.lib.vsig_boxcar_energy_dev(ctx.h, code, _ptr(x), 16, 5, _ptr(sm))
+    e = _DMAG ** 2
+    # differences of prefix sums, each off by at most n eps64 sum(e)
+    return rc, lambda: np.allclose(sm.cpu().numpy(), np.convolve(e, np.ones(5) / 5, "same"), rtol=0,
+                                   atol=2 * 16 * _EPS64 * e.sum())
+
+
+def _d_db(ctx, code):
+    x, out = _dev(_DR), _zeros(16, torch.float64)
+    rc = ctx.lib.vsig_db_dev(ctx.h, code, _ptr(x), 16, 1e-12, _ptr(out))
+    want = 10 * np.log10(np.abs(_DR) + 1e-12)
+    return rc, lambda: bool(np.all(np.abs(out.cpu().numpy() - want) <= 8 * np.spacing(np.abs(want))))   # as A2
+
+
+def _d_abs(ctx, code, wide):
+    x, out = _dev(_DX), _zeros(16, torch.complex128 if wide else torch.complex64)
+    fn = ctx.lib.vsig_abs_c128_dev if wide else ctx.lib.vsig_abs_c64_dev
+    rc = fn(ctx.h, code, _ptr(x), 16, _ptr(out))
+    want = _DMAG if wide else _DMAG.astype(np.float32)
+    return rc, lambda: np.array_equal(out.cpu().numpy(), want + 0j)
+
+
+def _d_image(ctx, code):
+    # a 4 x 4 map whose pixels sit in the middle of colour rows _DROWS; the table's entry i is the number i
+    vmin, vmax = -40.0, 0.0
+    s = 10.0 ** (((_DROWS + 0.5) / 256 * (vmax - vmin) + vmin) / 10)
+    x, lut, out = _dev(s), torch.arange(259, dtype=torch.int32, device="cuda"), _zeros(16, torch.int32)
+    rc = ctx.lib.vsig_spectrogram_image_dev(ctx.h, code, _ptr(x), 4, 4, 0, 4, 0.0, vmin, vmax, 0, 0, 1, 1, _ptr(lut),
+                                            _ptr(out))
+    return rc, lambda: out.tolist() == _DROWS.tolist()
+
+
+def _d_dft(ctx, code):
+    x, y = _dev(_DX), _zeros(16, torch.complex64)
+    rc = ctx.lib.vsig_dft_dev(ctx.h, code, _ptr(x), 16, 1, 0, _lib.DTYPES["c64"], _ptr(y))
+    return rc, lambda: np.allclose(y.cpu().numpy(), np.fft.fft(_DX), rtol=0, atol=_FFT_TOL)
+
+
+def _d_resample(ctx, code):
+    x, y = _dev(_DX), _zeros(8, torch.complex64)
+    rc = ctx.lib.vsig_resample_dev(ctx.h, code, _ptr(x), 16, 8, 0, _ptr(y))
+    return rc, lambda: np.allclose(y.cpu().numpy(), ref.resample_signal(_DX, 2.0, 1.0), rtol=0, atol=_FFT_TOL)
+
+
+def _d_channel(ctx, code):
+    # sample_rate 4, n 16: the reference's axis is CENTER_FREQ + k, the band keeps k = 1, 2, 3
+    x, y, args = _dev(_DX), _zeros(16, torch.float64), (ref.CENTER_FREQ + 2.0, 4.0, 3.0)
+    rc = ctx.lib.vsig_filter_channel_dev(ctx.h, code, _ptr(x), 16, *args, _ptr(y))
+    return rc, lambda: np.allclose(y.cpu().numpy(), ref.filter_channel(_DX, *args), rtol=0, atol=_FFT_TOL)
+
+
+def _d_correlate(ctx, code):
+    a, v, c = _dev(_DX), _dev(_DV), _zeros(13, torch.complex128)
+    rc = ctx.lib.vsig_correlate_dev(ctx.h, code, _ptr(a), 16, _ptr(v), 4, _lib.MODES["valid"], _lib.DTYPES["c128"],
+                                    _ptr(c), None)
+    # complex64 transforms of any length the library may pick (at most 2^14 points: 14 passes)
+    tol = 4 * 14 * _EPS32 * float(np.linalg.norm(_DX) * np.linalg.norm(_DV))
+    return rc, lambda: np.allclose(c.cpu().numpy(), np.correlate(_DX, _DV, "valid"), rtol=0, atol=tol)
+
+
+def _d_correlate_stats(ctx, code):
+    a, v, st = _dev(_DX), _dev(_DV), _zeros(2, torch.float64)
+    rc = ctx.lib.vsig_correlate_stats_dev(ctx.h, code, _ptr(a), 16, _ptr(v), 4, _lib.MODES["valid"], _ptr(st))
+    m = np.abs(np.correlate(_DX, _DV, "valid"))
+    # double sums of 4 products, then 13 magnitudes: 64 eps64 max|c| covers mean and std
+    return rc, lambda: np.allclose(st.cpu().numpy(), [m.mean(), m.std()], rtol=0, atol=64 * _EPS64 * m.max())
+
+
+# entry point -> (status for an unknown code, a valid code, the call)
+_DTYPE_ENTRIES = {
+    "vsig_peak_dev": (E_INVALID, "c128", _d_peak),
+    "vsig_peaks_dev": (E_INVALID, "c128", _d_peaks),
+    "vsig_trace_envelope_dev": (E_INVALID, "c128", _d_trace),
+    "vsig_abs_stats_dev": (E_UNSUPPORTED, "c128", _d_abs_stats),
+    "vsig_select_dev": (E_INVALID, "f64", _d_select),
+    "vsig_threshold_dev": (E_INVALID, "f64", _d_threshold),
+    "vsig_boxcar_energy_dev": (E_INVALID, "c128", _d_boxcar),
+    "vsig_db_dev": (E_HIP, "f64", _d_db),
+    "vsig_abs_c64_dev": (E_HIP, "c128", lambda ctx, code: _d_abs(ctx, code, False)),
+    "vsig_abs_c128_dev": (E_HIP, "c128", lambda ctx, code: _d_abs(ctx, code, True)),
+    "vsig_spectrogram_image_dev": (E_INVALID, "f64", _d_image),
+    "vsig_dft_dev": (E_INVALID, "c128", _d_dft),
+    "vsig_resample_dev": (E_INVALID, "c128", _d_resample),
+    "vsig_filter_channel_dev": (E_INVALID, "c128", _d_channel),
+    "vsig_correlate_dev": (E_INVALID, "c128", _d_correlate),
+    "vsig_correlate_stats_dev": (E_INVALID, "c128", _d_correlate_stats),
+}
+
+
+def test_d0_every_dtype_entry_point_is_listed():
+    """The table above names every *_dev entry point of the ABI whose second
+    argument is a dtype code (vsig_planar_to_c64_dev's is a MAT class)."""
+    have = {n for n, (_, args) in _lib.SIGNATURES.items()
+            if n.endswith("_dev") and len(args) > 2 and args[1] is _lib.I32 and n != "vsig_planar_to_c64_dev"}
+    assert have == set(_DTYPE_ENTRIES)
+
+
+@pytest.mark.parametrize("entry", sorted(_DTYPE_ENTRIES))
+def test_d1_unknown_dtype_code(gpu, entry):
+    status, code, call = _DTYPE_ENTRIES[entry]
+    ctx = gpu.get_context()
+    for bad in (4, -1):
+        rc, _ = call(ctx, bad)
+        assert rc == status, (entry, bad, rc, ctx.lib.vsig_last_error(ctx.h).decode())
+    rc, right = call(ctx, _lib.DTYPES[code])
+    assert rc == _lib.VSIG_OK, (entry, rc, ctx.lib.vsig_last_error(ctx.h).decode())
+    assert right(), entry

@@ -9,6 +9,7 @@ import ctypes as C
 import os
 import threading
 
+import numpy as np
 import torch  # loaded first: libvsig.so then binds torch's HIP runtime (same soname)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -17,6 +18,27 @@ LIB_PATH = os.path.join(HERE, "libvsig.so")
 VSIG_OK = 0
 MODES = {"valid": 0, "full": 1, "same": 2}
 DTYPES = {"c128": 0, "c64": 1, "f64": 2, "f32": 3}
+# the element types the |a| kernels take -> their name in DTYPES
+TORCH_CODES = {torch.complex128: "c128", torch.complex64: "c64", torch.float64: "f64", torch.float32: "f32"}
+NP_CODES = {np.dtype(np.complex128): "c128", np.dtype(np.complex64): "c64", np.dtype(np.float64): "f64",
+            np.dtype(np.float32): "f32"}
+
+
+def upload_native(x, ctx):
+    """(contiguous CUDA tensor, dtype name) of a numpy array or a tensor of any
+    shape: the four dtypes of DTYPES are kept, anything else is widened to
+    float64 / complex128 (as numpy's promotion would for np.abs)."""
+    if isinstance(x, torch.Tensor):
+        t = x if x.is_cuda else x.to(f"cuda:{ctx.device}")
+        if t.dtype not in TORCH_CODES:
+            t = t.to(torch.complex128 if t.is_complex() else torch.float64)
+    else:
+        a = np.asarray(x)
+        if a.dtype not in NP_CODES:
+            a = a.astype(np.complex128 if np.iscomplexobj(a) else np.float64)
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(f"cuda:{ctx.device}")
+    t = t.contiguous()
+    return t, TORCH_CODES[t.dtype]
 
 
 class VsigUnavailable(RuntimeError):

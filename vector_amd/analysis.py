@@ -25,35 +25,12 @@ from .dsp import _correlate_dev, _is_dev, _ptr
 __all__ = ["normalize_spectrogram", "spectrogram_levels", "find_packet_start", "detect_packet_bounds",
            "order_statistics", "threshold_stats", "boxcar_energy"]
 
-_TORCH_CODE = {torch.complex128: "c128", torch.complex64: "c64", torch.float64: "f64",
-               torch.float32: "f32"}
-_NP_CODE = {np.dtype(np.complex128): "c128", np.dtype(np.complex64): "c64",
-            np.dtype(np.float64): "f64", np.dtype(np.float32): "f32"}
-
-
 def _to_device(x, ctx, real_only=False):
-    """(flat contiguous CUDA tensor, dtype code) keeping numpy's dtype where the
-    kernels support it (other dtypes go to float64 / complex128 as numpy's
-    promotion would for these expressions)."""
-    if _is_dev(x):
-        t = x
-        if not t.is_cuda:
-            t = t.to(f"cuda:{ctx.device}")
-        code = _TORCH_CODE.get(t.dtype)
-        if code is None:
-            t = t.to(torch.complex128 if t.is_complex() else torch.float64)
-            code = _TORCH_CODE[t.dtype]
-        t = t.contiguous().reshape(-1)
-    else:
-        a = np.asarray(x)
-        code = _NP_CODE.get(a.dtype)
-        if code is None:
-            a = a.astype(np.complex128 if np.iscomplexobj(a) else np.float64)
-            code = _NP_CODE[a.dtype]
-        t = torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(f"cuda:{ctx.device}")
+    """_lib.upload_native, flattened; real_only refuses a complex array."""
+    t, code = _lib.upload_native(x, ctx)
     if real_only and code in ("c64", "c128"):
         raise ValueError("expected a real array")
-    return t, code
+    return t.reshape(-1), code
 
 
 def order_statistics(a, ranks):

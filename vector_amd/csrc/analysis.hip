@@ -17,9 +17,8 @@
 // allows); order statistics cost ceil(bits/8) histogram passes.
 #include <hip/hip_runtime.h>
 
-#include "vsig_kernels.h"
-#include "npabs.hpp"
 #include "dbmath.hpp"
+#include "dtype.hpp"
 
 namespace vsig {
 
@@ -67,7 +66,7 @@ __global__ __launch_bounds__(256) void radix_hist(const T* __restrict__ a, long 
   }
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-    const U k = Key<T>::of(fabs(a[i]));
+    const U k = Key<T>::of(mag(a[i]));
     const unsigned int d = (unsigned int)((k >> shift) & 0xff);
     for (int q = 0; q < nq; ++q)
       if ((k & mk[q]) == pf[q]) atomicAdd(&h[q][d], 1u);
@@ -87,9 +86,6 @@ struct ThreshPartial {
   double max;
 };
 
-// np.max's step: a NaN wins and then stays (nothing compares above it).
-__device__ __forceinline__ double np_max(double m, double v) { return (v > m || v != v) ? v : m; }
-
 template <class T>
 __global__ __launch_bounds__(256) void thresh_reduce(const T* __restrict__ a, long long n, double thr,
                                                      ThreshPartial* __restrict__ parts) {
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(256) void thresh_reduce(const T* __restrict__ a, lo
   double mx = -1.0 / 0.0;
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-    const double v = fabs((double)a[i]);
+    const double v = (double)mag(a[i]);
     if (v >= thr) {
       ++cnt;
       if (i < first) first = i;
@@ -134,21 +130,10 @@ __global__ __launch_bounds__(256) void thresh_reduce(const T* __restrict__ a, lo
 constexpr int SCAN_T = 256, SCAN_E = 16, SCAN_TILE = SCAN_T * SCAN_E;
 
 // |x|^2 exactly as numpy forms np.abs(x) ** 2 (squared in the abs's dtype).
-__device__ __forceinline__ double energy_of(const float2* x, long long i) {
-  const float2 v = x[i];
-  const float h = np_cabs(v.x, v.y);
-  return (double)__fmul_rn(h, h);
-}
-__device__ __forceinline__ double energy_of(const double2* x, long long i) {
-  const double2 v = x[i];
-  const double h = np_cabs(v.x, v.y);
-  return __dmul_rn(h, h);
-}
-__device__ __forceinline__ double energy_of(const float* x, long long i) {
-  return (double)__fmul_rn(x[i], x[i]);
-}
-__device__ __forceinline__ double energy_of(const double* x, long long i) {
-  return __dmul_rn(x[i], x[i]);
+__device__ __forceinline__ double sq_rn(float h) { return (double)__fmul_rn(h, h); }
+__device__ __forceinline__ double sq_rn(double h) { return __dmul_rn(h, h); }
+template <class T> __device__ __forceinline__ double energy_of(const T* x, long long i) {
+  return sq_rn(mag(x[i]));
 }
 
 template <int BT>
@@ -259,24 +244,16 @@ __global__ __launch_bounds__(256) void boxcar_direct(const T* __restrict__ x, lo
 // normalize_spectrogram's 10 * np.log10(|S| + floor) in the dtype numpy
 // evaluates it in (float32 S with a float32 floor stays float32): db_of
 // (dbmath.hpp; dB maps agree with numpy's to a few ulp, not bit-exact).
-__global__ __launch_bounds__(256) void db_transform_f64(const double* __restrict__ a, long long n,
-                                                        double floor_, double* __restrict__ out) {
-  const long long stride = (long long)gridDim.x * 256;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-    out[i] = db_of(a[i], floor_);
-}
-__global__ __launch_bounds__(256) void db_transform_f32(const float* __restrict__ a, long long n,
-                                                        float floor_, float* __restrict__ out) {
+template <class T>
+__global__ __launch_bounds__(256) void db_transform(const T* __restrict__ a, long long n, T floor_,
+                                                    T* __restrict__ out) {
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
     out[i] = db_of(a[i], floor_);
 }
 
-// |a| + 0j (np.abs as numpy computes it: complex -> np_cabs, real -> fabs),
-// written as complex64 (O = float2) or complex128 (O = double2).
-template <class T> __device__ __forceinline__ double absd(const T& v) { return np_cabs(v.x, v.y); }
-template <> __device__ __forceinline__ double absd<double>(const double& v) { return fabs(v); }
-template <> __device__ __forceinline__ double absd<float>(const float& v) { return (double)fabsf(v); }
+// |a| + 0j (np.abs as numpy computes it: mag), written as complex64
+// (O = float2) or complex128 (O = double2).
 template <class O> __device__ __forceinline__ O mk_re(double r);
 template <> __device__ __forceinline__ float2 mk_re<float2>(double r) { return make_float2((float)r, 0.f); }
 template <> __device__ __forceinline__ double2 mk_re<double2>(double r) { return make_double2(r, 0.0); }
@@ -286,7 +263,7 @@ __global__ __launch_bounds__(256) void abs_to_c(const T* __restrict__ a, long lo
                                                 O* __restrict__ out) {
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-    out[i] = mk_re<O>(absd<T>(a[i]));
+    out[i] = mk_re<O>((double)mag(a[i]));
 }
 
 // ---------------------------------------------------------------- launchers
@@ -300,28 +277,20 @@ hipError_t launch_radix_hist(int dtype, const void* a, long long n, const unsign
                              const unsigned long long* mask, int nq, int shift,
                              unsigned long long* hist, hipStream_t st) {
   const int g = grid_for(n) > 2048 ? 2048 : grid_for(n);
-  if (dtype == VSIG_F32)
-    hipLaunchKernelGGL(radix_hist<float>, dim3(g), dim3(256), 0, st, (const float*)a, n, prefix,
-                       mask, nq, shift, hist);
-  else if (dtype == VSIG_F64)
-    hipLaunchKernelGGL(radix_hist<double>, dim3(g), dim3(256), 0, st, (const double*)a, n, prefix,
-                       mask, nq, shift, hist);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  return dispatch_real(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(radix_hist<T>, dim3(g), dim3(256), 0, st, (const T*)a, n, prefix, mask, nq, shift, hist);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_thresh_reduce(int dtype, const void* a, long long n, double thr, void* parts,
                                 int nparts, hipStream_t st) {
-  if (dtype == VSIG_F32)
-    hipLaunchKernelGGL(thresh_reduce<float>, dim3(nparts), dim3(256), 0, st, (const float*)a, n,
-                       thr, (ThreshPartial*)parts);
-  else if (dtype == VSIG_F64)
-    hipLaunchKernelGGL(thresh_reduce<double>, dim3(nparts), dim3(256), 0, st, (const double*)a, n,
-                       thr, (ThreshPartial*)parts);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  return dispatch_real(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(thresh_reduce<T>, dim3(nparts), dim3(256), 0, st, (const T*)a, n, thr, (ThreshPartial*)parts);
+    return hipGetLastError();
+  });
 }
 
 long long energy_scan_tiles(long long n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
@@ -336,14 +305,10 @@ static void energy_prefix_t(const void* x, long long n, double* sums, double* P,
 
 hipError_t launch_energy_prefix(int dtype, const void* x, long long n, double* sums, double* P,
                                 hipStream_t st) {
-  switch (dtype) {
-    case VSIG_C128: energy_prefix_t<double2>(x, n, sums, P, st); break;
-    case VSIG_C64: energy_prefix_t<float2>(x, n, sums, P, st); break;
-    case VSIG_F64: energy_prefix_t<double>(x, n, sums, P, st); break;
-    case VSIG_F32: energy_prefix_t<float>(x, n, sums, P, st); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    energy_prefix_t<typename decltype(tag)::type>(x, n, sums, P, st);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_boxcar_same(const double* P, long long n, long long w, double* sm, hipStream_t st) {
@@ -357,41 +322,29 @@ hipError_t launch_boxcar_direct(int dtype, const void* x, long long n, long long
                                 hipStream_t st) {
   const long long nout = n > w ? n : w;
   const long long c = ((n < w ? n : w) - 1) / 2;
-  const dim3 g(grid_for(nout)), b(256);
-  switch (dtype) {
-    case VSIG_C128: hipLaunchKernelGGL(boxcar_direct<double2>, g, b, 0, st, (const double2*)x, n, w, nout, c, sm); break;
-    case VSIG_C64: hipLaunchKernelGGL(boxcar_direct<float2>, g, b, 0, st, (const float2*)x, n, w, nout, c, sm); break;
-    case VSIG_F64: hipLaunchKernelGGL(boxcar_direct<double>, g, b, 0, st, (const double*)x, n, w, nout, c, sm); break;
-    case VSIG_F32: hipLaunchKernelGGL(boxcar_direct<float>, g, b, 0, st, (const float*)x, n, w, nout, c, sm); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(boxcar_direct<T>, dim3(grid_for(nout)), dim3(256), 0, st, (const T*)x, n, w, nout, c, sm);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_db_transform(int dtype, const void* a, long long n, double floor_, void* out,
                                hipStream_t st) {
-  if (dtype == VSIG_F32)
-    hipLaunchKernelGGL(db_transform_f32, dim3(grid_for(n)), dim3(256), 0, st, (const float*)a, n,
-                       (float)floor_, (float*)out);
-  else if (dtype == VSIG_F64)
-    hipLaunchKernelGGL(db_transform_f64, dim3(grid_for(n)), dim3(256), 0, st, (const double*)a, n,
-                       floor_, (double*)out);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
+  return dispatch_real(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(db_transform<T>, dim3(grid_for(n)), dim3(256), 0, st, (const T*)a, n, (T)floor_, (T*)out);
+    return hipGetLastError();
+  });
 }
 
 template <class O>
 static hipError_t launch_abs_t(int dtype, const void* a, long long n, O* out, hipStream_t st) {
-  const int g = grid_for(n);
-  switch (dtype) {
-    case VSIG_C128: hipLaunchKernelGGL((abs_to_c<double2, O>), dim3(g), dim3(256), 0, st, (const double2*)a, n, out); break;
-    case VSIG_C64: hipLaunchKernelGGL((abs_to_c<float2, O>), dim3(g), dim3(256), 0, st, (const float2*)a, n, out); break;
-    case VSIG_F64: hipLaunchKernelGGL((abs_to_c<double, O>), dim3(g), dim3(256), 0, st, (const double*)a, n, out); break;
-    case VSIG_F32: hipLaunchKernelGGL((abs_to_c<float, O>), dim3(g), dim3(256), 0, st, (const float*)a, n, out); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((abs_to_c<T, O>), dim3(grid_for(n)), dim3(256), 0, st, (const T*)a, n, out);
+    return hipGetLastError();
+  });
 }
 hipError_t launch_abs_c64(int dtype, const void* a, long long n, float2* out, hipStream_t st) {
   return launch_abs_t<float2>(dtype, a, n, out, st);

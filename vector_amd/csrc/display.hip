@@ -37,7 +37,7 @@
 #include <cstdint>
 
 #include "dbmath.hpp"
-#include "vsig_kernels.h"
+#include "dtype.hpp"
 
 namespace vsig {
 
@@ -65,9 +65,6 @@ struct ImgGeom {
   int oxb, oyb;             // output pixels along x and y per block (oyb <= OYB)
   int flip;
 };
-
-// max that keeps a NaN from either side
-template <class T> __device__ __forceinline__ T nmax(T a, T b) { return (b > a || b != b) ? b : a; }
 
 template <class T, int N> struct Vec;
 template <> struct Vec<float, 4> { using type = float4; };
@@ -108,7 +105,7 @@ __device__ __forceinline__ void column_max(const T* __restrict__ p0, long long l
 #pragma unroll
     for (int b = 0; b < RB; ++b) {
 #pragma unroll
-      for (int k = 0; k < N; ++k) m[k] = nmax(m[k], (T)fabs(v[b][k]));
+      for (int k = 0; k < N; ++k) m[k] = np_max(m[k], mag(v[b][k]));
     }
   }
 }
@@ -196,7 +193,7 @@ __global__ __launch_bounds__(IT) void spectrogram_image(const T* __restrict__ S,
         b = b > g.nx ? g.nx : b;
         b = b > cx + XW ? cx + XW : b;
         T m = acc[j];
-        for (long long xx = a; xx < b; ++xx) m = nmax(m, L[oyl * PITCH + (int)(xx - cx)]);
+        for (long long xx = a; xx < b; ++xx) m = np_max(m, L[oyl * PITCH + (int)(xx - cx)]);
         acc[j] = m;
       }
     }
@@ -269,13 +266,11 @@ hipError_t launch_spectrogram_image(int dtype, const void* sxx, long long n_freq
   if (!sxx || !lut || !rgba || n_freq < 1 || n_time < 1 || pf < 1 || pt < 1 ||
       ld < (freq_fast ? n_freq : n_time))
     return hipErrorInvalidValue;
-  if (dtype == VSIG_F32)
-    return freq_fast ? image_t<float, true>(sxx, n_freq, n_time, ld, floor_, vmin, vmax, median, flip, pf, pt, lut, rgba, st)
-                     : image_t<float, false>(sxx, n_freq, n_time, ld, floor_, vmin, vmax, median, flip, pf, pt, lut, rgba, st);
-  if (dtype == VSIG_F64)
-    return freq_fast ? image_t<double, true>(sxx, n_freq, n_time, ld, floor_, vmin, vmax, median, flip, pf, pt, lut, rgba, st)
-                     : image_t<double, false>(sxx, n_freq, n_time, ld, floor_, vmin, vmax, median, flip, pf, pt, lut, rgba, st);
-  return hipErrorInvalidValue;
+  return dispatch_real(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return freq_fast ? image_t<T, true>(sxx, n_freq, n_time, ld, floor_, vmin, vmax, median, flip, pf, pt, lut, rgba, st)
+                     : image_t<T, false>(sxx, n_freq, n_time, ld, floor_, vmin, vmax, median, flip, pf, pt, lut, rgba, st);
+  });
 }
 
 }  // namespace vsig

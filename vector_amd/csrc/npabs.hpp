@@ -1,5 +1,6 @@
-// numpy's complex magnitude on the device (gfx950), shared by the |c| reductions
-// (reduce.hip), the refine (refine.hip) and the packet detectors (analysis.hip).
+// numpy's complex magnitude on the device (gfx950): what mag() of a complex
+// element is (dtype.hpp, through which every |a| kernel gets it); called on
+// separate parts by the refine (refine.hip), region.hip and vector_build.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -4,8 +4,7 @@
 // each, compiled in parallel; every kernel is launched from its own TU).
 #pragma once
 #include "fft_engine.hpp"
-#include "vsig_kernels.h"
-#include "npabs.hpp"
+#include "dtype.hpp"
 
 namespace vsig {
 
@@ -161,15 +160,8 @@ __device__ __forceinline__ void load_segment_mix(float2* v, const float2* __rest
 
 // ---------------------------------------------------------------------------
 // Block partial of a |c| reduction: max |c|^2 (lowest index on ties),
-// sum |c|, sum |c|^2.
+// sum |c|, sum |c|^2 (betterd: dtype.hpp).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void better(float& m, long long& i, float m2, long long i2) {
-  if (m2 > m || (m2 == m && i2 < i)) { m = m2; i = i2; }
-}
-__device__ __forceinline__ void betterd(double& m, long long& i, double m2, long long i2) {
-  if (m2 > m || (m2 == m && i2 < i)) { m = m2; i = i2; }
-}
-
 template <int BT>
 __device__ __forceinline__ void block_partial(double m, long long mi, double s1, double s2,
                                               PeakPartial* out) {

@@ -35,8 +35,7 @@
 // nothing but NaN has maximum -1 at its first index).
 #include <climits>
 
-#include "npabs.hpp"
-#include "vsig_kernels.h"
+#include "dtype.hpp"
 
 namespace vsig {
 
@@ -46,17 +45,6 @@ constexpr int PT = 256;                      // threads per block
 constexpr int PE = kPeaksTile / PT;          // elements per thread and tile
 constexpr int PG = 32;                       // tiles per block of the mark passes
 constexpr int PW = PT / 64;
-
-__device__ __forceinline__ double mag(double2 v) { return np_cabs(v.x, v.y); }
-__device__ __forceinline__ double mag(float2 v) { return (double)np_cabs(v.x, v.y); }
-__device__ __forceinline__ double mag(double v) { return fabs(v); }
-__device__ __forceinline__ double mag(float v) { return (double)fabsf(v); }
-
-__device__ __forceinline__ void first_max(double& m, long long& i, double m2, long long i2) {
-  if (m2 > m || (m2 == m && i2 < i)) { m = m2; i = i2; }
-}
-
-template <class T> struct alignas(16) Pack16 { T e[16 / sizeof(T)]; };
 
 // VEC: a is 16-byte aligned (whole tiles by 16-byte loads; the last, partial
 // tile and unaligned arrays element by element).
@@ -84,30 +72,30 @@ __global__ __launch_bounds__(PT) void peaks_tile(const T* __restrict__ a, long l
       for (int j = 0; j < NV; ++j)
 #pragma unroll
         for (int q = 0; q < EPV; ++q)
-          first_max(m, mi, mag(pk[j].e[q]), base + (long long)(j * PT + threadIdx.x) * EPV + q);
+          betterd(m, mi, (double)mag(pk[j].e[q]), base + (long long)(j * PT + threadIdx.x) * EPV + q);
     } else {
 #pragma unroll
       for (int e = 0; e < PE; ++e) {
         const long long g = base + e * PT + threadIdx.x;
-        if (g < n) first_max(m, mi, mag(a[g]), g);
+        if (g < n) betterd(m, mi, (double)mag(a[g]), g);
       }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       const double om = __shfl_xor(m, off);
       const long long oi = __shfl_xor(mi, off);
-      first_max(m, mi, om, oi);
+      betterd(m, mi, om, oi);
     }
     // sm / si alternate between tiles: one barrier a tile is enough
     if (lane == 0) { sm[par][w] = m; si[par][w] = mi; }
     __syncthreads();
     if (threadIdx.x == 0) {
-      for (int q = 1; q < PW; ++q) first_max(m, mi, sm[par][q], si[par][q]);
+      for (int q = 1; q < PW; ++q) betterd(m, mi, sm[par][q], si[par][q]);
       if (mi == LLONG_MAX) mi = base;        // nothing but NaN
       PeakPartial r;
       r.max2 = m; r.idx = mi; r.sum_abs = 0.0; r.sum_abs2 = 0.0;
       tab[tile] = r;
-      first_max(bm, bi, m, mi);
+      betterd(bm, bi, m, mi);
     }
   }
   if (threadIdx.x == 0) {                    // every block has at least one tile
@@ -153,8 +141,8 @@ __device__ bool beaten_outside(const PeaksArgs& A, long long t, double v, long l
   }
   // the partial tiles at the window's ends
   int hit = 0;
-  for (long long q = lo + threadIdx.x; q < jl * kPeaksTile; q += PT) hit |= mag(a[q]) >= v;
-  for (long long q = (jr + 1) * kPeaksTile + threadIdx.x; q <= hi; q += PT) hit |= mag(a[q]) > v;
+  for (long long q = lo + threadIdx.x; q < jl * kPeaksTile; q += PT) hit |= (double)mag(a[q]) >= v;
+  for (long long q = (jr + 1) * kPeaksTile + threadIdx.x; q <= hi; q += PT) hit |= (double)mag(a[q]) > v;
   return __syncthreads_or(hit) != 0;
 }
 
@@ -214,7 +202,7 @@ __global__ __launch_bounds__(PT) void peaks_mark(PeaksArgs A) {
     const long long ts = t * kPeaksTile;
     for (int i = threadIdx.x; i < kPeaksTile + 2 * H; i += PT) {
       const long long g = ts - H + i;
-      L[i] = (g >= 0 && g < A.n) ? mag(a[g]) : -1.0;
+      L[i] = (g >= 0 && g < A.n) ? (double)mag(a[g]) : -1.0;
     }
     __syncthreads();
     bool fl[PE];
@@ -368,13 +356,9 @@ size_t peaks_scratch_bytes(long long n) {
 hipError_t launch_peaks(int dtype, const void* a, long long n, double thr, int relative, long long d,
                         PeakInst* out, long long cap, PeaksInfo* info, void* scratch, hipStream_t st) {
   if (n < 1 || d < 0 || cap < 0 || !a || !info || !scratch || (cap > 0 && !out)) return hipErrorInvalidValue;
-  switch (dtype) {
-    case VSIG_C128: return peaks_t<double2>(a, n, thr, relative, d, out, cap, info, scratch, st);
-    case VSIG_C64: return peaks_t<float2>(a, n, thr, relative, d, out, cap, info, scratch, st);
-    case VSIG_F64: return peaks_t<double>(a, n, thr, relative, d, out, cap, info, scratch, st);
-    case VSIG_F32: return peaks_t<float>(a, n, thr, relative, d, out, cap, info, scratch, st);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return peaks_t<typename decltype(tag)::type>(a, n, thr, relative, d, out, cap, info, scratch, st);
+  });
 }
 
 }  // namespace vsig

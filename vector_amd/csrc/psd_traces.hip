@@ -41,10 +41,6 @@ constexpr int kMinUnits = 4;                 // steps a block runs at least (whe
 constexpr int kMergeT = 1024, kMergeG = kMergeT / 64;   // merge: 64 bins x 16 row groups
 constexpr int kFoldT = 256, kFoldG = kFoldT / 64;       // fold: 64 bins x 4 frame groups
 
-// np.max / np.min of two values: a NaN on either side stays
-__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
-__device__ __forceinline__ float nan_min(float a, float b) { return (b < a || b != b) ? b : a; }
-
 __device__ __forceinline__ PsdRec rec_identity() {
   PsdRec r;
   r.sum = 0.0; r.mx = -__builtin_inff(); r.mn = __builtin_inff();
@@ -52,8 +48,8 @@ __device__ __forceinline__ PsdRec rec_identity() {
 }
 __device__ __forceinline__ void rec_fold(PsdRec& a, const PsdRec& b) {
   a.sum += b.sum;
-  a.mx = nan_max(a.mx, b.mx);
-  a.mn = nan_min(a.mn, b.mn);
+  a.mx = np_max(a.mx, b.mx);
+  a.mn = np_min(a.mn, b.mn);
 }
 
 // The accumulators of a thread's E bins (fully unrolled: registers).
@@ -70,8 +66,8 @@ struct Acc {
     for (int e = 0; e < E; ++e) {
       const float p = (v[e].x * v[e].x + v[e].y * v[e].y) * scale;
       s[e] += (double)p;
-      mx[e] = nan_max(mx[e], p);
-      mn[e] = nan_min(mn[e], p);
+      mx[e] = np_max(mx[e], p);
+      mn[e] = np_min(mn[e], p);
     }
   }
   __device__ __forceinline__ PsdRec rec(int e) const {
@@ -237,8 +233,8 @@ __global__ __launch_bounds__(kFoldT) void psd_traces_fold(const float* __restric
     for (long long f = (long long)blockIdx.y * kFoldG + g; f < nb; f += (long long)kPsdFoldRows * kFoldG) {
       const float p = sxx[f * N + k];
       a.sum += (double)p;
-      a.mx = nan_max(a.mx, p);
-      a.mn = nan_min(a.mn, p);
+      a.mx = np_max(a.mx, p);
+      a.mn = np_min(a.mn, p);
     }
   }
   sm[g][lane] = a;

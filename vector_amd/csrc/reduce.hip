@@ -10,16 +10,6 @@ namespace vsig {
 // precision), first max wins.
 // T = double2 (complex128), float2 (complex64), double, float.
 // ---------------------------------------------------------------------------
-template <class T> __device__ __forceinline__ double absval(const T* p, long long i);
-template <> __device__ __forceinline__ double absval<double2>(const double2* p, long long i) {
-  const double2 v = p[i]; return np_cabs(v.x, v.y);
-}
-template <> __device__ __forceinline__ double absval<float2>(const float2* p, long long i) {
-  const float2 v = p[i]; return (double)np_cabs(v.x, v.y);
-}
-template <> __device__ __forceinline__ double absval<double>(const double* p, long long i) { return fabs(p[i]); }
-template <> __device__ __forceinline__ double absval<float>(const float* p, long long i) { return (double)fabsf(p[i]); }
-
 template <class T>
 __global__ __launch_bounds__(256) void peak_reduce(const T* __restrict__ a, long long n,
                                                    PeakPartial* __restrict__ partials) {
@@ -27,7 +17,7 @@ __global__ __launch_bounds__(256) void peak_reduce(const T* __restrict__ a, long
   long long mi = 0x7fffffffffffffffLL;
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-    const double v = absval<T>(a, i);
+    const double v = (double)mag(a[i]);
     betterd(m, mi, v, i);
     s1 += v;
     s2 += v * v;
@@ -46,7 +36,7 @@ __global__ __launch_bounds__(1024) void peak_first_nan(const T* __restrict__ a, 
   if (rec->sum_abs == rec->sum_abs) return;              // uniform: every thread reads the same word
   long long first = 0x7fffffffffffffffLL;
   for (long long i = threadIdx.x; i < n; i += 1024) {
-    const double v = absval<T>(a, i);
+    const double v = (double)mag(a[i]);
     if (v != v) { first = i; break; }
   }
 #pragma unroll
@@ -67,14 +57,11 @@ __global__ __launch_bounds__(1024) void peak_first_nan(const T* __restrict__ a, 
 }
 
 hipError_t launch_peak_first_nan(int dtype, const void* a, long long n, PeakPartial* rec, hipStream_t st) {
-  switch (dtype) {
-    case VSIG_C128: hipLaunchKernelGGL(peak_first_nan<double2>, dim3(1), dim3(1024), 0, st, (const double2*)a, n, rec); break;
-    case VSIG_C64: hipLaunchKernelGGL(peak_first_nan<float2>, dim3(1), dim3(1024), 0, st, (const float2*)a, n, rec); break;
-    case VSIG_F64: hipLaunchKernelGGL(peak_first_nan<double>, dim3(1), dim3(1024), 0, st, (const double*)a, n, rec); break;
-    case VSIG_F32: hipLaunchKernelGGL(peak_first_nan<float>, dim3(1), dim3(1024), 0, st, (const float*)a, n, rec); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(peak_first_nan<T>, dim3(1), dim3(1024), 0, st, static_cast<const T*>(a), n, rec);
+    return hipGetLastError();
+  });
 }
 
 // Fixed-order reduction of nparts partials into out[0]; sqrt_max converts a
@@ -120,14 +107,11 @@ __global__ __launch_bounds__(256) void partial_chunks(const PeakPartial* __restr
 
 hipError_t launch_peak_reduce(int dtype, const void* a, long long n, PeakPartial* partials,
                               int nparts, hipStream_t st) {
-  switch (dtype) {
-    case VSIG_C128: hipLaunchKernelGGL(peak_reduce<double2>, dim3(nparts), dim3(256), 0, st, (const double2*)a, n, partials); break;
-    case VSIG_C64: hipLaunchKernelGGL(peak_reduce<float2>, dim3(nparts), dim3(256), 0, st, (const float2*)a, n, partials); break;
-    case VSIG_F64: hipLaunchKernelGGL(peak_reduce<double>, dim3(nparts), dim3(256), 0, st, (const double*)a, n, partials); break;
-    case VSIG_F32: hipLaunchKernelGGL(peak_reduce<float>, dim3(nparts), dim3(256), 0, st, (const float*)a, n, partials); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(peak_reduce<T>, dim3(nparts), dim3(256), 0, st, static_cast<const T*>(a), n, partials);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_partial_finalize(const PeakPartial* parts, long long nparts, int sqrt_max,
@@ -168,7 +152,7 @@ constexpr int kNpBuf = 8192;
 
 template <class T>
 __device__ __forceinline__ double np_elem(const T* __restrict__ a, long long i, int sq, double mean) {
-  double x = absval<T>(a, i);
+  double x = (double)mag(a[i]);
   if (sq) {
     x = x - mean;
     x = x * x;
@@ -295,22 +279,18 @@ hipError_t launch_np_stats(int dtype, const void* a, long long n, double* out, v
   const long long nb = (n + kNpBuf - 1) / kNpBuf;
   const unsigned grid = (unsigned)((nb + 3) / 4);
   double* bsum = static_cast<double*>(scratch);
-  for (int sq = 0; sq < 2; ++sq) {
-    switch (dtype) {
-      case VSIG_C128:
-        hipLaunchKernelGGL(np_buf_sums<double2>, dim3(grid), dim3(256), 0, st,
-                           static_cast<const double2*>(a), n, out, sq, bsum);
-        break;
-      case VSIG_F64:
-        hipLaunchKernelGGL(np_buf_sums<double>, dim3(grid), dim3(256), 0, st,
-                           static_cast<const double*>(a), n, out, sq, bsum);
-        break;
-      default:
-        return hipErrorInvalidValue;
+  return dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if constexpr (sizeof(typename Real<T>::type) == sizeof(double)) {   // complex128 / float64 only
+      for (int sq = 0; sq < 2; ++sq) {
+        hipLaunchKernelGGL(np_buf_sums<T>, dim3(grid), dim3(256), 0, st, static_cast<const T*>(a), n, out, sq, bsum);
+        hipLaunchKernelGGL(np_finish, dim3(1), dim3(256), 0, st, bsum, nb, n, sq, out);
+      }
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
     }
-    hipLaunchKernelGGL(np_finish, dim3(1), dim3(256), 0, st, bsum, nb, n, sq, out);
-  }
-  return hipGetLastError();
+  });
 }
 
 }  // namespace vsig

@@ -36,8 +36,7 @@
 #include <climits>
 
 #include "dbmath.hpp"
-#include "npabs.hpp"
-#include "vsig_kernels.h"
+#include "dtype.hpp"
 
 namespace vsig {
 
@@ -50,29 +49,10 @@ constexpr long long kTraceChunks = 8192;     // trace_chunks: blocks aimed at
 
 #pragma clang fp contract(off)
 
-template <class T> struct Real { using type = double; };
-template <> struct Real<float2> { using type = float; };
-template <> struct Real<float> { using type = float; };
-
-// np.abs of a complex value: np_cabs, and NaN where a part is NaN and none is
-// infinite (np_cabs alone gives 0 for NaN + 0j, whose larger part compares as 0)
-template <class R> __device__ __forceinline__ R cabs_nan(R re, R im) {
-  const R m = np_cabs(re, im);
-  return ((re != re) || (im != im)) && !isinf(m) ? (R)__builtin_nan("") : m;
-}
-__device__ __forceinline__ double mag(double2 v) { return cabs_nan(v.x, v.y); }
-__device__ __forceinline__ float mag(float2 v) { return cabs_nan(v.x, v.y); }
-__device__ __forceinline__ double mag(double v) { return fabs(v); }
-__device__ __forceinline__ float mag(float v) { return fabsf(v); }
-
 __device__ __forceinline__ void clear(double2& v) { v.x = 0.0; v.y = 0.0; }
 __device__ __forceinline__ void clear(float2& v) { v.x = 0.f; v.y = 0.f; }
 __device__ __forceinline__ void clear(double& v) { v = 0.0; }
 __device__ __forceinline__ void clear(float& v) { v = 0.f; }
-
-// np.max / np.min of two values: a NaN on either side stays
-template <class R> __device__ __forceinline__ R nan_max(R a, R b) { return (b > a || b != b) ? b : a; }
-template <class R> __device__ __forceinline__ R nan_min(R a, R b) { return (b < a || b != b) ? b : a; }
 
 template <class R> __device__ __forceinline__ R mapped(R e, int kind, double eps) {
   return kind == kTraceDb20 ? db20_of(e, (R)eps) : e;
@@ -88,9 +68,7 @@ struct Ext {
   __device__ __forceinline__ void init() {
     mx = (R)-1; mn = (R)__builtin_inf(); pmx = LLONG_MAX; pmn = LLONG_MAX; nan = 0;
   }
-  __device__ __forceinline__ void take_max(R v, long long p) {
-    if (v > mx || (v == mx && p < pmx)) { mx = v; pmx = p; }
-  }
+  __device__ __forceinline__ void take_max(R v, long long p) { betterd(mx, pmx, v, p); }
   __device__ __forceinline__ void take_min(R v, long long p) {
     if (v < mn || (v == mn && p < pmn)) { mn = v; pmn = p; }
   }
@@ -139,8 +117,6 @@ __device__ __forceinline__ void block_record(Ext<R> e, TraceRec* out) {
     *out = e.rec();
   }
 }
-
-template <class T> struct alignas(16) Pack16 { T e[16 / sizeof(T)]; };
 
 struct TraceArgs {
   const void* a;
@@ -233,15 +209,15 @@ __global__ __launch_bounds__(TT) void trace_cols(TraceArgs A) {
       const int qa = c * bin, qe = qa + bin < len ? qa + bin : len;
       for (int k = qa + gl; k < qe; k += G) {
         const R v = sm[k];
-        mx = nan_max(mx, v);
-        mn = nan_min(mn, v);
+        mx = np_max(mx, v);
+        mn = np_min(mn, v);
       }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       if (off < G) {                                           // partners stay inside the group
-        mx = nan_max(mx, __shfl_xor(mx, off));
-        mn = nan_min(mn, __shfl_xor(mn, off));
+        mx = np_max(mx, __shfl_xor(mx, off));
+        mn = np_min(mn, __shfl_xor(mn, off));
       }
     }
     // the column's results go where its first two magnitudes were (its group
@@ -384,13 +360,9 @@ hipError_t launch_trace_envelope(int dtype, const void* a, long long n, int shif
   A.a = a; A.n = n; A.rot = shift ? (n + 1) / 2 : 0; A.lo = lo; A.hi = hi; A.bin = bin;
   A.kind = kind; A.eps = eps; A.env_min = env_min; A.env_max = env_max;
   TraceRec* recs = static_cast<TraceRec*>(scratch);
-  switch (dtype) {
-    case VSIG_C128: return trace_t<double2>(A, p, info, recs, st);
-    case VSIG_C64: return trace_t<float2>(A, p, info, recs, st);
-    case VSIG_F64: return trace_t<double>(A, p, info, recs, st);
-    case VSIG_F32: return trace_t<float>(A, p, info, recs, st);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return trace_t<typename decltype(tag)::type>(A, p, info, recs, st);
+  });
 }
 
 }  // namespace vsig

@@ -11,9 +11,13 @@
 #include <vector>
 
 #include "../../include/vsig.h"
-#include "vsig_kernels.h"
+#include "dtype.hpp"
 
 using vsig::PeakPartial;
+using vsig::dtype_bytes;
+using vsig::dtype_ok;
+static_assert(VSIG_DTYPE_C128 == vsig::VSIG_C128 && VSIG_DTYPE_C64 == vsig::VSIG_C64 &&
+              VSIG_DTYPE_F64 == vsig::VSIG_F64 && VSIG_DTYPE_F32 == vsig::VSIG_F32, "VSIG_DTYPE_*");
 
 struct TimingRec {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
@@ -1551,7 +1555,7 @@ int vsig_correlate(vsig_ctx* c, int32_t dtype, const void* a, int64_t na, const 
   if (na < 1 || nv < 1) return fail(c, VSIG_E_INVALID, "empty input");
   if (!is_complex_dtype(dtype) || !is_complex_dtype(out_dtype))
     return fail(c, VSIG_E_INVALID, "dtype must be VSIG_DTYPE_C64 or VSIG_DTYPE_C128");
-  const size_t es = dtype == VSIG_DTYPE_C128 ? 16 : 8, eo = out_dtype == VSIG_DTYPE_C128 ? 16 : 8;
+  const size_t es = dtype_bytes(dtype), eo = dtype_bytes(out_dtype);
   long long F, nout;
   if (!corr_span(mode, na, nv, &F, &nout)) return fail(c, VSIG_E_INVALID, "mode must be VALID, FULL or SAME");
   int rc;
@@ -1668,7 +1672,7 @@ int vsig_filter_channel_dev(vsig_ctx* c, int32_t dtype, const void* x, int64_t n
 int vsig_peak_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, vsig_peak_t* peak_dev) {
   if (!c || !a) return fail(c, VSIG_E_INVALID, "null pointer");
   if (n < 1) return fail(c, VSIG_E_INVALID, "empty input");  // np.argmax of empty raises
-  if (dtype < VSIG_DTYPE_C128 || dtype > VSIG_DTYPE_F32) return fail(c, VSIG_E_INVALID, "dtype");
+  if (!dtype_ok(dtype)) return fail(c, VSIG_E_INVALID, "dtype");
   long long nparts = (n + 255) / 256;
   if (nparts > 2048) nparts = 2048;
   int rc = ensure_partials(c, nparts);
@@ -1686,9 +1690,9 @@ int vsig_peak_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, vsig_pea
 int vsig_peak(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, vsig_peak_t* peak) {
   if (!c || !a || !peak) return fail(c, VSIG_E_INVALID, "null pointer");
   if (n < 1) return fail(c, VSIG_E_INVALID, "empty input");
-  const size_t es = dtype == VSIG_DTYPE_C128 ? 16 : (dtype == VSIG_DTYPE_F32 ? 4 : 8);
   int rc;
-  if ((rc = stage_in(c, 0, a, (size_t)n * es)) || (rc = vsig_peak_dev(c, dtype, c->stage[0].data(), n, nullptr)) ||
+  if ((rc = stage_in(c, 0, a, (size_t)n * dtype_bytes(dtype))) ||
+      (rc = vsig_peak_dev(c, dtype, c->stage[0].data(), n, nullptr)) ||
       (rc = stage_out(c, peak, c->result, sizeof(vsig_peak_t))))
     return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1708,7 +1712,7 @@ static int peaks_check(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, dou
   if (!c || !a || !info) return fail(c, VSIG_E_INVALID, "null pointer");
   if (n < 1) return fail(c, VSIG_E_INVALID, "empty input");
   if (n > (1LL << 40)) return fail(c, VSIG_E_INVALID, "n above 2^40");
-  if (dtype < VSIG_DTYPE_C128 || dtype > VSIG_DTYPE_F32) return fail(c, VSIG_E_INVALID, "dtype");
+  if (!dtype_ok(dtype)) return fail(c, VSIG_E_INVALID, "dtype");
   if (cap < 0 || min_distance < 0) return fail(c, VSIG_E_INVALID, "need cap >= 0 and min_distance >= 0");
   if (cap > 0 && !out) return fail(c, VSIG_E_INVALID, "null out with cap > 0");
   if (thr != thr) return fail(c, VSIG_E_INVALID, "thr is NaN");
@@ -1731,10 +1735,9 @@ int vsig_peaks(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, double thr,
                int64_t min_distance, vsig_instance_t* out, int64_t cap, vsig_peaks_info_t* info) {
   int rc = peaks_check(c, dtype, a, n, thr, min_distance, out, cap, info);
   if (rc) return rc;
-  const size_t es = dtype == VSIG_DTYPE_C128 ? 16 : (dtype == VSIG_DTYPE_F32 ? 4 : 8);
   // stage[1]: the info record, then the instance records
   const size_t ib = sizeof(vsig_peaks_info_t);
-  if ((rc = stage_in(c, 0, a, (size_t)n * es)) ||
+  if ((rc = stage_in(c, 0, a, (size_t)n * dtype_bytes(dtype))) ||
       (rc = c->stage[1].reserve(c, ib + (size_t)cap * sizeof(vsig_instance_t))))
     return rc;
   char* sb = c->stage[1].as<char>();
@@ -1779,7 +1782,7 @@ int vsig_trace_envelope_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n
   if (!c || !a || !env_max_dev) return fail(c, VSIG_E_INVALID, "null pointer");
   if (n < 1) return fail(c, VSIG_E_INVALID, "empty input");
   if (n > (1LL << 40)) return fail(c, VSIG_E_INVALID, "n above 2^40");
-  if (dtype < VSIG_DTYPE_C128 || dtype > VSIG_DTYPE_F32) return fail(c, VSIG_E_INVALID, "dtype");
+  if (!dtype_ok(dtype)) return fail(c, VSIG_E_INVALID, "dtype");
   if (kind != VSIG_TRACE_ABS && kind != VSIG_TRACE_DB20) return fail(c, VSIG_E_INVALID, "kind");
   if (lo < 0 || hi > n || lo >= hi) return fail(c, VSIG_E_INVALID, "need 0 <= lo < hi <= n");
   if (bin < 1) return fail(c, VSIG_E_INVALID, "need bin >= 1");
@@ -2026,7 +2029,7 @@ int vsig_threshold_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, dou
     cnt += p.count;
     f = p.first < f ? p.first : f;
     l = p.last > l ? p.last : l;
-    mx = (p.max > mx || p.max != p.max) ? p.max : mx;     // np.max: a NaN wins and stays
+    mx = vsig::np_max(mx, p.max);
   }
   *count = cnt;
   *first = f;
@@ -2038,7 +2041,7 @@ int vsig_threshold_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, dou
 int vsig_boxcar_energy_dev(vsig_ctx* c, int32_t dtype, const void* x, int64_t n, int64_t w,
                            double* sm) {
   if (!c || !x || !sm) return fail(c, VSIG_E_INVALID, "null pointer");
-  if (dtype < VSIG_DTYPE_C128 || dtype > VSIG_DTYPE_F32) return fail(c, VSIG_E_INVALID, "dtype");
+  if (!dtype_ok(dtype)) return fail(c, VSIG_E_INVALID, "dtype");
   if (n < 1 || w < 1) return fail(c, VSIG_E_INVALID, "need n >= 1, w >= 1");
   const long long nt = vsig::energy_scan_tiles(n);
   int rc;

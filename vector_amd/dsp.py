@@ -583,35 +583,11 @@ def cross_correlate_signals(signal1, signal2, mode="full"):
 correlate = cross_correlate_signals
 
 
-def _stats_operand(a, ctx):
-    """a as a contiguous CUDA tensor and its dtype code."""
-    if _is_dev(a):
-        t = a.contiguous()
-        code = {torch.complex128: "c128", torch.complex64: "c64", torch.float64: "f64",
-                torch.float32: "f32"}.get(t.dtype)
-        if code is None:
-            t, code = t.to(torch.float64), "f64"
-    else:
-        arr = np.asarray(a)
-        if arr.dtype == np.complex128:
-            code = "c128"
-        elif arr.dtype == np.complex64:
-            code = "c64"
-        elif arr.dtype == np.float32:
-            code = "f32"
-        elif np.iscomplexobj(arr):
-            arr, code = arr.astype(np.complex128), "c128"
-        else:
-            arr, code = arr.astype(np.float64), "f64"
-        t = torch.from_numpy(np.ascontiguousarray(arr.ravel())).to(f"cuda:{ctx.device}")
-    return t, code
-
-
 def peak_stats(a):
     """(argmax of |a| (first), max |a|, sum |a|, sum |a|^2, n) in double
     precision on the GPU, for numpy or CUDA arrays of complex/real dtype."""
     ctx = _lib.get_context()
-    t, code = _stats_operand(a, ctx)
+    t, code = _lib.upload_native(a, ctx)
     n = int(t.numel())
     if n == 0:
         raise ValueError("attempt to get argmax of an empty sequence")
@@ -627,7 +603,7 @@ def find_correlation_peak(correlation, lags, threshold_ratio=0.5):
     of |c| exactly as numpy forms them (its pairwise sums, two passes); other
     dtypes: from double sums of |c| (single pass)."""
     ctx = _lib.get_context()
-    t, code = _stats_operand(correlation, ctx)
+    t, code = _lib.upload_native(correlation, ctx)
     n = int(t.numel())
     if n == 0:
         raise ValueError("attempt to get argmax of an empty sequence")
@@ -1005,12 +981,9 @@ def find_peaks(a, threshold, min_distance=0, relative=False, max_peaks=65536):
     ``info.view(torch.float64)[2:]``)."""
     _check_peaks_args(threshold, min_distance, max_peaks)
     ctx = _lib.get_context()
-    if _is_dev(a):
-        if a.dim() != 1:
-            raise ValueError("vector_amd works on 1-D signals")
-        if not a.is_cuda:
-            a = a.to(f"cuda:{ctx.device}")
-    t, code = _stats_operand(a, ctx)
+    if _is_dev(a) and a.dim() != 1:
+        raise ValueError("vector_amd works on 1-D signals")
+    t, code = _lib.upload_native(a, ctx)
     idx, val, info = _peaks_dev(t, code, threshold, min_distance, relative, max_peaks, ctx)
     if _is_dev(a):
         return idx, val, info

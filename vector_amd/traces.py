@@ -43,8 +43,6 @@ __all__ = ["Trace", "trace_bin", "trace_envelope", "time_axis", "spectrum_axis",
 
 Trace = namedtuple("Trace", "x lo hi bin argmax max")
 
-_CODES = {torch.complex128: "c128", torch.complex64: "c64", torch.float64: "f64", torch.float32: "f32"}
-
 
 def trace_bin(n, max_points):
     """Positions per column of a line of n points drawn with at most
@@ -76,22 +74,6 @@ def _out_dtype(a, dev):
     return torch.float32 if a.dtype in (np.dtype(np.complex64), np.dtype(np.float32)) else torch.float64
 
 
-def _to_device(a, ctx):
-    """A contiguous 1-D CUDA tensor of one of the four dtypes (other real /
-    complex dtypes are widened to float64 / complex128, as np.abs would)."""
-    if _is_dev(a):
-        t = a if a.is_cuda else a.to(f"cuda:{ctx.device}")
-    else:
-        try:
-            t = torch.from_numpy(a)
-        except (ValueError, TypeError):                  # negative strides, odd dtypes
-            t = torch.from_numpy(np.ascontiguousarray(a, np.complex128 if np.iscomplexobj(a) else np.float64))
-        t = t.to(f"cuda:{ctx.device}")
-    if t.dtype not in _CODES:
-        t = t.to(torch.complex128 if t.is_complex() else torch.float64)
-    return t.contiguous()
-
-
 def trace_envelope(t, *, shift=False, lo=0, hi=None, bin=1, db=False, eps=0.0, want_min=True, ctx=None):
     """vsig_trace_envelope_dev on a contiguous 1-D CUDA tensor of one of the
     four dtypes -> (env_min or None, env_max, info): the envelope tensors in
@@ -106,7 +88,7 @@ def trace_envelope(t, *, shift=False, lo=0, hi=None, bin=1, db=False, eps=0.0, w
     emin = torch.empty(cols, dtype=real, device=t.device) if want_min else None
     info = torch.empty(4, dtype=torch.int64, device=t.device)
     ctx.check(ctx.lib.vsig_trace_envelope_dev(
-        ctx.h, _lib.DTYPES[_CODES[t.dtype]], _ptr(t), n, int(bool(shift)), lo, hi, bin,
+        ctx.h, _lib.DTYPES[_lib.TORCH_CODES[t.dtype]], _ptr(t), n, int(bool(shift)), lo, hi, bin,
         _lib.TRACE_DB20 if db else _lib.TRACE_ABS, float(eps), _ptr(emin) if want_min else None, _ptr(emax),
         _ptr(info)), "trace envelope")
     return emin, emax, info
@@ -166,7 +148,7 @@ def signal_envelope(signal, sample_rate=None, *, start=0, stop=None, max_points=
     if stop <= start:
         return _empty(dev_in, signal.device if dev_in else None, real, bin_)
     ctx = _lib.get_context(signal.device.index if dev_in and signal.is_cuda else None)
-    t = _to_device(signal[start:stop], ctx)
+    t, _ = _lib.upload_native(signal[start:stop], ctx)
     emin, emax, info = trace_envelope(t, bin=bin_, db=db, eps=eps, want_min=bin_ > 1, ctx=ctx)
     _, argmax, _, mx = _read_info(info)
     x = time_axis(start, stop, bin_, sample_rate)
@@ -287,13 +269,13 @@ def capture_spectrum(data, sample_rate, center_freq=0.0, *, scale="db", eps=0.0,
         return _empty(dev_in, data.device if dev_in else None, real, bin_)
 
     ctx = _lib.get_context(data.device.index if dev_in and data.is_cuda else None)
-    t = _to_device(data, ctx)
+    t, _ = _lib.upload_native(data, ctx)
     if remove_dc:
         t = t - t.mean()
     if not t.is_complex():
         t = t.to(torch.complex128 if t.dtype == torch.float64 else torch.complex64)
     X = torch.empty(n, dtype=torch.complex64, device=t.device)
-    ctx.check(ctx.lib.vsig_dft_dev(ctx.h, _lib.DTYPES[_CODES[t.dtype]], _ptr(t), n, 1, 0, _lib.DTYPES["c64"],
+    ctx.check(ctx.lib.vsig_dft_dev(ctx.h, _lib.DTYPES[_lib.TORCH_CODES[t.dtype]], _ptr(t), n, 1, 0, _lib.DTYPES["c64"],
                                    _ptr(X)), "dft")
     db = scale == "db"
     emin, emax, info = trace_envelope(X, shift=shift, lo=lo_p, hi=hi_p, bin=bin_, db=db, eps=eps,
@@ -369,7 +351,7 @@ def averaged_spectrum_trace(data, sample_rate, center_freq=0.0, *, nfft=8192, wi
     ctx = _lib.get_context(line.device.index)
     emin, emax, info = trace_envelope(line, bin=bin_, want_min=bin_ > 1, ctx=ctx)
     if scale == "db":
-        code = _lib.DTYPES[_CODES[line.dtype]]
+        code = _lib.DTYPES[_lib.TORCH_CODES[line.dtype]]
 
         def db(t):
             o = torch.empty_like(t)
