@@ -539,6 +539,59 @@ int vsig_peaks_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, doubl
 int vsig_peaks(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, double thr, int32_t relative,
                int64_t min_distance, vsig_instance_t* out, int64_t cap, vsig_peaks_info_t* info);
 
+/* ---- run list: every burst of an array, where vsig_threshold_dev stops at the
+ * first and last index above the threshold.  With m[i] = |a[i]| as
+ * vsig_peak_dev forms it (numpy's abs in the array's precision, widened to
+ * double; any VSIG_DTYPE_*) and mask[i] = m[i] >= thr, a run is a maximal
+ * interval [start, end] (end inclusive) whose two ends are in the mask and in
+ * which no stretch of more than max_gap consecutive elements is outside it.
+ * Per index: a masked i is a start iff the previous masked index p (or -inf)
+ * has i - p > max_gap + 1, an end iff the next masked index q (or +inf) has
+ * q - i > max_gap + 1; the k-th start pairs with the k-th end.  In numpy:
+ *   idx = np.flatnonzero(m >= thr); brk = np.flatnonzero(np.diff(idx) > max_gap + 1)
+ *   start = idx[np.r_[0, brk + 1]]; end = idx[np.r_[brk, idx.size - 1]]
+ * So max_gap = 0 gives the plain runs of the mask, any max_gap >= n at most
+ * the one run [first, last] of vsig_threshold_dev, and start[0] / end[-1]
+ * never depend on max_gap.  thr is absolute, or with relative != 0 a ratio:
+ * thr_used = thr * max(m), one double multiply on the device.
+ * Per run: max / argmax the first maximum of m over [start, end] (gaps
+ *   included), sum = the sum of m over [start, end] in double, in a fixed order.
+ * out: the runs in ascending order, at most cap records (the cap lowest-index
+ *   ones when there are more); may be NULL when cap == 0 (count only).
+ *   Records past min(count, cap) are not written.
+ * info: always written; count is the exact number of runs whatever cap,
+ *   covered the number of masked elements, argmax / max those of the array.
+ * The same input gives the same bytes on every run.  Cost: one pass over the
+ * array, a second read of the tiles that hold both masked and unmasked
+ * elements, and per run its two end tiles; nothing proportional to max_gap.
+ * n < 1, n > 2^40, cap < 0, max_gap < 0, a NULL a / info, a NULL out with
+ * cap > 0, an unknown dtype or a NaN thr: VSIG_E_INVALID before any work is
+ * enqueued.  Arrays that hold NaN are outside the contract: a NaN element is
+ * not masked, and all writes stay inside out[0..cap) and info.
+ * vsig_runs_dev enqueues on the context stream, allocates nothing once its
+ * scratch is warm for n and never synchronises (capturable).  vsig_runs takes
+ * host pointers (a, out, info) and returns when they are filled.
+ * vsig_runs_tile: the kernels' tile length (elements). */
+typedef struct vsig_run_t {
+  int64_t start;     /* first index of the run */
+  int64_t end;       /* last index of the run (inclusive) */
+  int64_t argmax;    /* index of the first max of |a| over [start, end] */
+  double max;        /* that maximum */
+  double sum;        /* sum of |a| over [start, end] */
+} vsig_run_t;
+typedef struct vsig_runs_info_t {
+  int64_t count;     /* runs in the array */
+  int64_t covered;   /* elements with |a| >= thr_used */
+  int64_t argmax;    /* index of the first max of |a| */
+  double max;        /* max |a| */
+  double thr_used;   /* the threshold applied */
+} vsig_runs_info_t;
+int vsig_runs_tile(void);
+int vsig_runs_dev(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, double thr, int32_t relative,
+                  int64_t max_gap, vsig_run_t* out_dev, int64_t cap, vsig_runs_info_t* info_dev);
+int vsig_runs(vsig_ctx* ctx, int32_t dtype, const void* a, int64_t n, double thr, int32_t relative,
+              int64_t max_gap, vsig_run_t* out, int64_t cap, vsig_runs_info_t* info);
+
 /* ---- line traces: the lines the reference draws beside every spectrogram --
  * np.abs(signal) over time (utils.py:551-554, 853-856, 939, 1090) and the
  * magnitude, or 20 log10 of it, of a whole-capture spectrum over frequency

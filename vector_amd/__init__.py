@@ -8,7 +8,8 @@ a HIP device every call raises ``VsigUnavailable``.
 from ._lib import (RefineFault, VsigError, VsigInvalid, VsigUnavailable, get_context,  # noqa: F401
                    load_library)
 from . import dsp  # noqa: F401
-from .dsp import (Correlator, CorrelatorBank, FirFilter, FrequencySearch, SpectrumTraces,  # noqa: F401
+from .dsp import (Correlator, CorrelatorBank, FirFilter, FrequencySearch, Runs, SpectrumTraces,  # noqa: F401
+                  find_runs,
                   averaged_spectrum, correlate, correlate_peak,
                   cross_correlate_signals, filter, find_correlation_peak,
                   find_packet_instances, find_packet_location_in_vector,
@@ -21,8 +22,8 @@ from .vectors import (apply_frequency_shift, resample_signal, load_packet, load_
                       extract_reference_segment, measure_packet_timing, validate_transplant_quality,
                       transplant_and_validate,
                       VectorPlan, build_vector, compute_freq_ranges, validate_packet_timing, vector_plan,
-                      verify_vector)
-from .analysis import (boxcar_energy, detect_packet_bounds, find_packet_start,  # noqa: F401
+                      verify_vector, extract_packets)
+from .analysis import (Packets, boxcar_energy, detect_packet_bounds, detect_packets, find_packet_start,  # noqa: F401
                        normalize_spectrogram, order_statistics, threshold_stats)
 from .display import (SpectrogramImage, colormap_table, image_extent, plot_spectrogram_image,  # noqa: F401
                       pool_factors, spectrogram_image, spectrogram_levels)

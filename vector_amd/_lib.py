@@ -99,6 +99,17 @@ class PeaksInfo(C.Structure):
     _fields_ = [("count", I64), ("argmax", I64), ("max", C.c_double), ("thr_used", C.c_double)]
 
 
+class Run(C.Structure):
+    """vsig_run_t (include/vsig.h)."""
+    _fields_ = [("start", I64), ("end", I64), ("argmax", I64), ("max", C.c_double), ("sum", C.c_double)]
+
+
+class RunsInfo(C.Structure):
+    """vsig_runs_info_t (include/vsig.h)."""
+    _fields_ = [("count", I64), ("covered", I64), ("argmax", I64), ("max", C.c_double),
+                ("thr_used", C.c_double)]
+
+
 class TraceInfo(C.Structure):
     """vsig_trace_info_t (include/vsig.h)."""
     _fields_ = [("argmin", I64), ("argmax", I64), ("min", C.c_double), ("max", C.c_double)]
@@ -162,6 +173,9 @@ SIGNATURES = {
     "vsig_peaks_tile": (C.c_int, []),
     "vsig_peaks_dev": (C.c_int, [P, I32, P, I64, C.c_double, I32, I64, P, I64, P]),
     "vsig_peaks": (C.c_int, [P, I32, P, I64, C.c_double, I32, I64, P, I64, P]),
+    "vsig_runs_tile": (C.c_int, []),
+    "vsig_runs_dev": (C.c_int, [P, I32, P, I64, C.c_double, I32, I64, P, I64, P]),
+    "vsig_runs": (C.c_int, [P, I32, P, I64, C.c_double, I32, I64, P, I64, P]),
     "vsig_abs_stats_dev": (C.c_int, [P, I32, P, I64, P]),
     "vsig_correlate_stats_dev": (C.c_int, [P, I32, P, I64, P, I64, I32, P]),
     "vsig_region_power_dev": (C.c_int, [P, P, P, I64, P]),

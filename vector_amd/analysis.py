@@ -4,6 +4,7 @@ rows a3, a7, a8):
   normalize_spectrogram   utils.py:356-404  (spectrogram_levels: its level selection alone)
   find_packet_start       utils.py:784-809
   detect_packet_bounds    utils.py:811-825
+  detect_packets          every burst of the same smoothed energy (the run list, runs.hip)
 
 The data-parallel work — |S| order statistics, the dB transform, the |x|^2
 prefix scan and boxcar smoothing, the threshold scan, the magnitude
@@ -15,15 +16,16 @@ give the same numbers the reference computes.
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from .dsp import _correlate_dev, _is_dev, _ptr
+from .dsp import _correlate_dev, _is_dev, _ptr, _runs_host
 
 __all__ = ["normalize_spectrogram", "spectrogram_levels", "find_packet_start", "detect_packet_bounds",
-           "order_statistics", "threshold_stats", "boxcar_energy"]
+           "order_statistics", "threshold_stats", "boxcar_energy", "detect_packets", "Packets"]
 
 def _to_device(x, ctx, real_only=False):
     """_lib.upload_native, flattened; real_only refuses a complex array."""
@@ -269,9 +271,8 @@ def normalize_spectrogram(Sxx, low_percentile=10.0, high_percentile=95.0, max_dy
 # ---------------------------------------------------------------------------
 # find_packet_start / detect_packet_bounds — utils.py:784-825
 # ---------------------------------------------------------------------------
-def _threshold_first_last(ctx, sm, m, threshold_ratio):
-    """noise = median(sm[:m]), thr = noise + r (max - noise), first / last
-    index of sm >= thr (count 0 -> None)."""
+def _energy_threshold(ctx, sm, m, threshold_ratio):
+    """(noise, thr): noise = median(sm[:m]), thr = noise + r (max - noise)."""
     head = sm[:m]
     cache = {}
 
@@ -283,7 +284,13 @@ def _threshold_first_last(ctx, sm, m, threshold_ratio):
 
     noise = _median(m, np.float64, fetch)
     _, _, _, max_en = _thresh_dev(ctx, sm, "f64", np.inf)
-    threshold = noise + threshold_ratio * (np.float64(max_en) - noise)
+    return noise, noise + threshold_ratio * (np.float64(max_en) - noise)
+
+
+def _threshold_first_last(ctx, sm, m, threshold_ratio):
+    """First / last index of sm >= _energy_threshold's thr (a NaN thr or
+    count 0 -> None)."""
+    _, threshold = _energy_threshold(ctx, sm, m, threshold_ratio)
     if np.isnan(threshold):
         return None
     cnt, first, last, _ = _thresh_dev(ctx, sm, "f64", float(threshold))
@@ -338,3 +345,66 @@ def detect_packet_bounds(signal, sample_rate, threshold_ratio=0.2):
     if r is None:
         return 0, n
     return np.int64(r[0]), np.int64(r[1])
+
+
+# ---------------------------------------------------------------------------
+# detect_packets — every burst of a capture, where detect_packet_bounds
+# returns the first and last sample above its threshold
+# ---------------------------------------------------------------------------
+class Packets(NamedTuple):
+    """detect_packets' result: one entry per burst in starts / ends (inclusive)
+    / peak_index / peak / mean_power, and the scalars the rule used."""
+    starts: np.ndarray        # int64: first sample of the smoothed energy at or above the threshold
+    ends: np.ndarray          # int64: last one (inclusive)
+    peak_index: np.ndarray    # int64: first maximum of the smoothed energy inside the burst
+    peak: np.ndarray          # float64: that maximum
+    mean_power: np.ndarray    # float64: mean smoothed energy over [start, end]
+    noise: float              # median of the first tenth of the smoothed energy (nan with ``threshold``)
+    threshold: float          # the level applied
+    window: int               # boxcar length, samples
+
+
+def detect_packets(signal, sample_rate, threshold_ratio=0.2, max_gap=None, min_length=None,
+                   threshold=None, max_packets=65536):
+    """Where every burst of ``signal`` begins and ends, without a template:
+    the runs (find_runs' definition, vsig_runs_dev) of detect_packet_bounds'
+    own smoothed energy ``sm = np.convolve(np.abs(x) ** 2, np.ones(w) / w,
+    'same')``, ``w = max(1, int(sample_rate // 1e6))``, at or above its own
+    threshold ``noise + threshold_ratio * (max(sm) - noise)``, noise the median
+    of sm's first tenth.  ``threshold`` replaces that rule by an absolute
+    level on sm.
+
+    max_gap and min_length default to w: a dropout shorter than the smoother
+    cannot separate two packets and a burst shorter than it is not resolved.
+    With min_length=1 and any max_gap, ``(starts[0], ends[-1])`` is
+    detect_packet_bounds' pair.  Nothing above the threshold, or a NaN
+    threshold, gives an empty list (not detect_packet_bounds' (0, n)).
+
+    Returns ``Packets`` with host arrays (numpy or CUDA tensor in).  More than
+    max_packets bursts (counted before min_length): one more call with room
+    for all when there are at most 2**24, else a RuntimeWarning and the first
+    max_packets."""
+    w = max(1, int(sample_rate // 1_000_000))
+    max_gap = w if max_gap is None else int(max_gap)
+    min_length = w if min_length is None else int(min_length)
+    if max_gap < 0:
+        raise ValueError("max_gap must be >= 0")
+    if min_length < 1:
+        raise ValueError("min_length must be >= 1")
+    if int(max_packets) < 0:
+        raise ValueError("max_packets must be >= 0")
+    if (int(signal.numel()) if isinstance(signal, torch.Tensor) else int(np.size(signal))) == 0:
+        raise ValueError("detect_packets of an empty signal")
+    ctx = _lib.get_context()
+    t, code = _to_device(signal, ctx)
+    sm = _boxcar_dev(ctx, t, code, w)
+    if threshold is None:
+        noise, thr = _energy_threshold(ctx, sm, max(1, int(sm.numel()) // 10), threshold_ratio)
+    else:
+        noise, thr = np.float64(np.nan), np.float64(threshold)
+    if np.isnan(thr):
+        e = np.zeros(0, np.int64)
+        f = np.zeros(0, np.float64)
+        return Packets(e, e.copy(), e.copy(), f, f.copy(), float(noise), float(thr), w)
+    r, _ = _runs_host(sm, "f64", float(thr), max_gap, False, min_length, max_packets, ctx, "detect_packets")
+    return Packets(r.start, r.end, r.argmax, r.max, r.mean, float(noise), float(thr), w)

@@ -93,6 +93,7 @@ struct vsig_ctx {
   DevBuf vscratch;                       // numpy-order |c| of every output (exact stats)
   DevBuf sscratch;                       // np_stats buffer sums
   DevBuf pscratch;                       // peaks.hip tile table, counts, offsets
+  DevBuf rnscratch;                      // runs.hip tile table, mask words, per-group records
   DevBuf gscratch;                       // region.hip per-block partials
   DevBuf tscratch;                       // trace.hip per-block / per-chunk / per-column records
   DevBuf ptscratch;                      // psd_traces.hip record rows (+ the fold route's frame batch)
@@ -1751,6 +1752,62 @@ int vsig_peaks(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, double thr,
   const int64_t k = h.count < cap ? h.count : cap;
   if (k > 0) {
     HIPCHK(c, hipMemcpyAsync(out, od, (size_t)k * sizeof(vsig_instance_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  *info = h;
+  return VSIG_OK;
+}
+
+// ---------------------------------------------------------------- run list
+static_assert(sizeof(vsig_run_t) == sizeof(vsig::RunRec) && sizeof(vsig_run_t) == 40, "vsig_run_t layout");
+static_assert(sizeof(vsig_runs_info_t) == sizeof(vsig::RunsInfo) && sizeof(vsig_runs_info_t) == 40,
+              "vsig_runs_info_t layout");
+
+int vsig_runs_tile(void) { return vsig::kRunsTile; }
+
+static int runs_check(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, double thr, int64_t max_gap,
+                      const void* out, int64_t cap, const void* info) {
+  if (!c || !a || !info) return fail(c, VSIG_E_INVALID, "null pointer");
+  if (n < 1) return fail(c, VSIG_E_INVALID, "empty input");
+  if (n > (1LL << 40)) return fail(c, VSIG_E_INVALID, "n above 2^40");
+  if (!dtype_ok(dtype)) return fail(c, VSIG_E_INVALID, "dtype");
+  if (cap < 0 || max_gap < 0) return fail(c, VSIG_E_INVALID, "need cap >= 0 and max_gap >= 0");
+  if (cap > 0 && !out) return fail(c, VSIG_E_INVALID, "null out with cap > 0");
+  if (thr != thr) return fail(c, VSIG_E_INVALID, "thr is NaN");
+  return VSIG_OK;
+}
+
+int vsig_runs_dev(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, double thr, int32_t relative,
+                  int64_t max_gap, vsig_run_t* out_dev, int64_t cap, vsig_runs_info_t* info_dev) {
+  int rc = runs_check(c, dtype, a, n, thr, max_gap, out_dev, cap, info_dev);
+  if (rc || (rc = c->rnscratch.reserve(c, vsig::runs_scratch_bytes(n)))) return rc;
+  Timed t(c, "runs");
+  HIPCHK(c, vsig::launch_runs(dtype, a, n, thr, relative != 0, max_gap,
+                              reinterpret_cast<vsig::RunRec*>(out_dev), cap,
+                              reinterpret_cast<vsig::RunsInfo*>(info_dev), c->rnscratch.data(), c->stream));
+  return VSIG_OK;
+}
+
+int vsig_runs(vsig_ctx* c, int32_t dtype, const void* a, int64_t n, double thr, int32_t relative,
+              int64_t max_gap, vsig_run_t* out, int64_t cap, vsig_runs_info_t* info) {
+  int rc = runs_check(c, dtype, a, n, thr, max_gap, out, cap, info);
+  if (rc) return rc;
+  // stage[1]: the info record, then the run records
+  const size_t ib = sizeof(vsig_runs_info_t);
+  if ((rc = stage_in(c, 0, a, (size_t)n * dtype_bytes(dtype))) ||
+      (rc = c->stage[1].reserve(c, ib + (size_t)cap * sizeof(vsig_run_t))))
+    return rc;
+  char* sb = c->stage[1].as<char>();
+  vsig_run_t* od = cap > 0 ? reinterpret_cast<vsig_run_t*>(sb + ib) : nullptr;
+  if ((rc = vsig_runs_dev(c, dtype, c->stage[0].data(), n, thr, relative, max_gap, od, cap,
+                          reinterpret_cast<vsig_runs_info_t*>(sb))))
+    return rc;
+  vsig_runs_info_t h;
+  HIPCHK(c, hipMemcpyAsync(&h, sb, ib, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int64_t k = h.count < cap ? h.count : cap;
+  if (k > 0) {
+    HIPCHK(c, hipMemcpyAsync(out, od, (size_t)k * sizeof(vsig_run_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   *info = h;

@@ -406,6 +406,17 @@ size_t peaks_scratch_bytes(long long n);
 hipError_t launch_peaks(int dtype, const void* a, long long n, double thr, int relative, long long d,
                         PeakInst* out, long long cap, PeaksInfo* info, void* scratch, hipStream_t st);
 
+// runs.hip: the run list of |a| >= thr (maximal intervals whose ends are
+// masked and that hold no more than max_gap unmasked elements in a row; see
+// the file's header).  thr / relative / out / cap / info as for launch_peaks.
+// scratch: runs_scratch_bytes(n).
+constexpr int kRunsTile = 2048;
+struct RunRec { long long start, end, argmax; double max, sum; };           // = vsig_run_t
+struct RunsInfo { long long count, covered, argmax; double max, thr_used; };  // = vsig_runs_info_t
+size_t runs_scratch_bytes(long long n);
+hipError_t launch_runs(int dtype, const void* a, long long n, double thr, int relative, long long max_gap,
+                       RunRec* out, long long cap, RunsInfo* info, void* scratch, hipStream_t st);
+
 // trace.hip: the min / max envelope of |a| per column of `bin` positions of
 // the (optionally fftshifted) line over [lo, hi), and the window's first
 // extrema (vsig_trace_envelope_dev; see include/vsig.h).  env_min / info may

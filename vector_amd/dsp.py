@@ -32,7 +32,7 @@ from .windows import get_window
 __all__ = ["spectrum", "averaged_spectrum", "SpectrumTraces", "filter", "fir_filter", "correlate", "correlate_peak",
            "cross_correlate_signals", "find_correlation_peak",
            "find_packet_location_in_vector", "FirFilter", "Correlator", "peak_stats",
-           "refine_status", "check_refine", "find_peaks", "find_packet_instances",
+           "refine_status", "check_refine", "find_peaks", "find_packet_instances", "find_runs", "Runs",
            "CorrelatorBank", "FrequencySearch", "frequency_search", "find_packet_location_with_offset"]
 
 PEAK_BYTES = 32  # sizeof(vsig_peak_t)
@@ -1037,6 +1037,107 @@ def find_packet_instances(vector, packet, threshold_ratio=0.5, min_distance=None
     if _is_dev(vector) or _is_dev(packet):
         return idx, val
     return _trim_peaks(idx, val, info, int(max_instances), "find_packet_instances")
+
+
+# ---------------------------------------------------------------------------
+# run list — every burst, where threshold_stats stops at the first and last index
+# ---------------------------------------------------------------------------
+Runs = namedtuple("Runs", ["start", "end", "argmax", "max", "mean"])
+RUN_WORDS = C.sizeof(_lib.Run) // 8            # a record as int64 words: start, end, argmax, max, sum
+MAX_RETRY_RUNS = 1 << 24                       # the largest exact count find_runs re-runs for
+
+
+def _check_runs_args(threshold, max_gap, min_length, max_runs):
+    if np.isnan(threshold):
+        raise ValueError("threshold must not be NaN")
+    if int(max_gap) < 0:
+        raise ValueError("max_gap must be >= 0")
+    if int(min_length) < 1:
+        raise ValueError("min_length must be >= 1")
+    if int(max_runs) < 0:
+        raise ValueError("max_runs must be >= 0")
+
+
+def _runs_dev(t, code, threshold, max_gap, relative, cap, ctx):
+    """vsig_runs_dev on a contiguous CUDA tensor: (records int64[cap, 5], info
+    int64[5]) on the device, nothing synchronised.  A record is vsig_run_t as
+    int64 words (-1 / 0 past the count), info is vsig_runs_info_t."""
+    cap = int(cap)
+    rec = torch.empty((cap, RUN_WORDS), dtype=torch.int64, device=t.device)
+    rec[:, :3] = -1
+    rec[:, 3:] = 0
+    info = torch.empty(RUN_WORDS, dtype=torch.int64, device=t.device)
+    ctx.check(ctx.lib.vsig_runs_dev(ctx.h, _lib.DTYPES[code], _ptr(t), int(t.numel()), float(threshold),
+                                    1 if relative else 0, int(max_gap), _ptr(rec) if cap else None, cap,
+                                    _ptr(info)), "runs")
+    return rec, info
+
+
+def _runs_host(t, code, threshold, max_gap, relative, min_length, max_runs, ctx, what):
+    """The run list of a device array on the host (Runs, info as a host int64
+    tensor): one more call with cap = count when the list overflowed max_runs
+    and the count allows it, then the min_length mask on the device."""
+    max_runs = int(max_runs)
+    rec, info = _runs_dev(t, code, threshold, max_gap, relative, max_runs, ctx)
+    h = info.cpu()
+    count = int(h[0])
+    k = min(count, max_runs)
+    if count > max_runs:
+        if count <= MAX_RETRY_RUNS:
+            rec, _ = _runs_dev(t, code, threshold, max_gap, relative, count, ctx)
+            k = count
+        else:
+            warnings.warn(f"{what}: {count} runs, the first {max_runs} are returned",
+                          RuntimeWarning, stacklevel=3)
+    rec = rec[:k]
+    if int(min_length) > 1:
+        rec = rec[(rec[:, 1] - rec[:, 0] + 1) >= int(min_length)]
+    r = rec.cpu().numpy().reshape(-1, RUN_WORDS)
+    start, end = r[:, 0].copy(), r[:, 1].copy()
+    mx = np.ascontiguousarray(r[:, 3]).view(np.float64)
+    mean = np.ascontiguousarray(r[:, 4]).view(np.float64) / (end - start + 1)
+    return Runs(start, end, r[:, 2].copy(), mx, mean), h
+
+
+def find_runs(a, threshold, max_gap=0, min_length=1, relative=False, max_runs=65536):
+    """The runs of ``m = |a| >= threshold`` (complex or real, numpy's abs in
+    a's precision): every maximal interval ``[start, end]`` (end inclusive)
+    whose ends are at or above the threshold and that holds no stretch of more
+    than max_gap consecutive elements below it -- in ascending order, found on
+    the GPU (vsig_runs_dev).  relative=True: the threshold is ``threshold *
+    max(m)``.  In numpy::
+
+        idx = np.flatnonzero(m >= thr)
+        brk = np.flatnonzero(np.diff(idx) > max_gap + 1)
+        start = idx[np.r_[0, brk + 1]]; end = idx[np.r_[brk, idx.size - 1]]
+
+    max_gap=0 gives the plain runs of the mask; a max_gap of len(a) or more at
+    most the one run (first, last).  min_length keeps the runs with
+    ``end - start + 1 >= min_length`` (applied after the kernel).
+
+    numpy in -> ``Runs(start, end, argmax, max, mean)`` arrays trimmed to the
+    count: argmax / max the first maximum of m over the run (gaps included),
+    mean its average.  With more than max_runs runs (counted before
+    min_length) the call is repeated once with room for all of them when there
+    are at most 2**24; beyond that a RuntimeWarning and the first max_runs.
+    CUDA tensor in -> ``(records, info)`` device tensors, nothing
+    synchronised and nothing retried: records int64[max_runs, 5] holding
+    vsig_run_t (start, end, argmax; max and sum as float64 bits; -1 / 0 past
+    the count), info int64[5] holding vsig_runs_info_t; min_length must be 1."""
+    _check_runs_args(threshold, max_gap, min_length, max_runs)
+    dev = _is_dev(a)
+    if dev and a.dim() != 1:
+        raise ValueError("vector_amd works on 1-D signals")
+    if (int(a.numel()) if isinstance(a, torch.Tensor) else int(np.size(a))) == 0:
+        raise ValueError("find_runs of an empty array")
+    if dev and int(min_length) != 1:
+        raise ValueError("min_length must be 1 for a CUDA tensor (the records stay on the device)")
+    ctx = _lib.get_context()
+    t, code = _lib.upload_native(a, ctx)
+    t = t.reshape(-1)
+    if dev:
+        return _runs_dev(t, code, threshold, max_gap, relative, max_runs, ctx)
+    return _runs_host(t, code, threshold, max_gap, relative, min_length, max_runs, ctx, "find_runs")[0]
 
 
 def find_packet_location_in_vector(vector, packet_signal, reference_segment,

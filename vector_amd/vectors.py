@@ -4,6 +4,8 @@
   apply_frequency_shift        utils.py:120-127            mix_c64 kernel
   transplant_packet_in_vector  utils.py:1437-1501          |x|^2 sums + scale_c64
   extract_reference_segment    utils.py:1345-1369          host (a slice)
+  extract_packets              the bursts detect_packets lists, with margins
+                                                           host (slices)
   measure_packet_timing        utils.py:827-846            find_packet_start
   validate_transplant_quality  utils.py:1504-1591          correlate_peak + region_power kernel
   transplant_and_validate      unified_gui.py:1087-1233    the four transplant steps in one call
@@ -40,7 +42,8 @@ from .dsp import (_device_c64, _is_dev, _ptr, correlate_peak, find_packet_instan
                   find_packet_location_in_vector, peak_stats)
 
 __all__ = ["apply_frequency_shift", "resample_signal", "transplant_packet_in_vector",
-           "extract_reference_segment", "measure_packet_timing", "validate_transplant_quality",
+           "extract_reference_segment", "extract_packets", "measure_packet_timing",
+           "validate_transplant_quality",
            "transplant_and_validate", "mat2wv", "save_vector_wv",
            "load_packet", "load_packet_info", "save_vector", "read_mat", "write_mat_vector",
            "VectorPlan", "vector_plan", "build_vector", "compute_freq_ranges",
@@ -179,6 +182,33 @@ def extract_reference_segment(signal, start_sample, end_sample):
     if start_sample >= end_sample:
         raise ValueError("Invalid sample range: start_sample >= end_sample")
     return signal[start_sample:end_sample]
+
+
+def extract_packets(signal, packets, pre_samples=0, post_samples=0):
+    """The slices of ``signal`` that hold the bursts of ``packets``
+    (detect_packets' result, or any sequence of inclusive ``(start, end)``
+    pairs): ``[(signal[max(0, s - pre_samples):min(n, e + 1 + post_samples)],
+    pre), ...]``, pre the lead-in actually applied (``pre_samples``, less
+    where the signal starts first) -- the value load_packet_info /
+    write_mat_vector carry beside a packet.  Views: numpy arrays and device
+    tensors alike.  Host only: no device, no library.  ValueError for a
+    negative margin or a burst that is not inside the signal."""
+    pre_samples, post_samples = int(pre_samples), int(post_samples)
+    if pre_samples < 0 or post_samples < 0:
+        raise ValueError("pre_samples and post_samples must be >= 0")
+    if hasattr(packets, "starts") and hasattr(packets, "ends"):
+        pairs = zip(packets.starts, packets.ends)
+    else:
+        pairs = packets
+    n = len(signal)
+    out = []
+    for s, e in pairs:
+        s, e = int(s), int(e)
+        if s < 0 or e >= n or s > e:
+            raise ValueError(f"burst ({s}, {e}) is not inside the signal ({n} samples)")
+        lo = max(0, s - pre_samples)
+        out.append((signal[lo:min(n, e + 1 + post_samples)], s - lo))
+    return out
 
 
 def measure_packet_timing(signal, template=None):
