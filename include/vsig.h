@@ -434,6 +434,12 @@ int vsig_normalize_c64_dev(vsig_ctx* ctx, const void* x, int64_t n, const float*
  * nframes = (n - ntaps) / nchan + 1; y frame-major (nframes x nchan). */
 int vsig_pfb_c64_dev(vsig_ctx* ctx, const void* x, int64_t n, const float* h, int32_t ntaps,
                      int32_t nchan, void* y, int64_t nframes);
+/* the geometry the call will use, for tests and tools: a launched block holds
+ * groups_per_block lane groups, group g of the grid owns the frames
+ * [g * frames_per_group, (g + 1) * frames_per_group); blocks = the grid for nframes.
+ * No context needed.  Another nchan / ntaps than above: VSIG_E_UNSUPPORTED. */
+int vsig_pfb_plan(int32_t nchan, int32_t ntaps, int64_t nframes, int64_t* frames_per_group,
+                  int64_t* groups_per_block, int64_t* blocks);
 
 /* ---- analysis (normalize_spectrogram utils.py:356-404, find_packet_start /
  * detect_packet_bounds utils.py:784-825).  All operate on |a|.

@@ -19,6 +19,17 @@ from oracle import ref
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "display.npz")
 UNDER, OVER, BAD = 256, 257, 258
+FLOOR, VMIN, VMAX = 1e-7, -60.0, -35.0      # the levels of the GPU tests' synthetic maps
+
+
+def centred(nf, nt, dt):
+    """Sxx whose dB values sit at the centres of bins k[i, j], a pattern that
+    tells neighbours, rows, columns and 64-cell tiles apart."""
+    i, j = np.meshgrid(np.arange(nf), np.arange(nt), indexing="ij")
+    k = (i * 7 + j * 13 + (i // 64) * 3 + (j // 64) * 5 + (i // 16) + (j // 256) * 11) % 256
+    S = 10 ** ((VMIN + (k + 0.5) / 256 * (VMAX - VMIN)) / 10) - FLOOR
+    assert S.min() > 0
+    return S.astype(dt)
 
 
 def noise_floor(S):

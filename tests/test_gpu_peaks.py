@@ -12,8 +12,8 @@ import ctypes as C
 import numpy as np
 import pytest
 import torch
-from scipy.ndimage import maximum_filter1d
 
+from peaks_ref import ref_peaks
 from vector_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -26,27 +26,6 @@ NP_CODE = {np.dtype(np.complex128): "c128", np.dtype(np.complex64): "c64",
 
 def mags(a):
     return np.abs(a).astype(np.float64)
-
-
-def ref_peaks(m, thr, d):
-    """(indices, values) of the instances of m (float64) by the definition."""
-    n = len(m)
-    w = min(int(d), n)
-    mx = maximum_filter1d(m, 2 * w + 1, mode="constant", cval=-np.inf)
-    cand = np.flatnonzero((m == mx) & (m >= thr))
-    # a candidate equals its window's maximum, so it is the FIRST maximum iff
-    # no equal element lies within d to its left: the previous index holding
-    # the same value, from a stable sort
-    order = np.argsort(m, kind="stable")
-    prev = np.full(n, -1, np.int64)
-    same = m[order[1:]] == m[order[:-1]]
-    prev[order[1:][same]] = order[:-1][same]
-    keep = cand[(prev[cand] < 0) | (cand - prev[cand] > d)]
-    if len(cand) * (2 * w + 1) <= 2e7:           # the literal rule where it is affordable
-        lit = [i for i in cand
-               if max(0, i - d) + np.argmax(m[max(0, i - d):min(n - 1, i + d) + 1]) == i]
-        assert np.array_equal(keep, np.asarray(lit, np.int64))
-    return keep.astype(np.int64), m[keep]
 
 
 def dev_peaks(va, t, code, thr, relative, d, cap, null_out=False):

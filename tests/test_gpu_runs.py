@@ -14,45 +14,11 @@ import numpy as np
 import pytest
 import torch
 
-import test_gpu_special_values as sv
 from conftest import golden
 from runs_ref import run_stats, runs_ref
 from vector_amd import _lib
 
 pytestmark = pytest.mark.gpu
-
-
-# ---------------------------------------------------------------------------
-# tests/test_gpu_special_values.py keeps a table of every *_dev entry point
-# whose second argument is a dtype code, and a test that the table is complete.
-# vsig_runs_dev is such an entry point; its row is added here, in the table's
-# own form (status for an unknown code, a valid code, the call), when this
-# file is imported -- which collecting the suite does before any test runs.
-# That file's parametrised unknown-code test was expanded before this row
-# existed, so the same check of the row is test_unknown_dtype_code below.
-# ---------------------------------------------------------------------------
-def _d_runs(ctx, code):
-    x = sv._dev(sv._DX)
-    out = torch.zeros(10, dtype=torch.int64, device="cuda")
-    info = torch.zeros(5, dtype=torch.int64, device="cuda")
-    rc = ctx.lib.vsig_runs_dev(ctx.h, code, sv._ptr(x), 16, 0.0, 0, 0, sv._ptr(out), 2, sv._ptr(info))
-    am, mx = int(sv._DMAG.argmax()), float(sv._DMAG.max())
-    return rc, lambda: (info[:3].tolist() == [1, 16, am] and out[:3].tolist() == [0, 15, am]
-                        and out.view(torch.float64)[3].item() == mx)
-
-
-sv._DTYPE_ENTRIES.setdefault("vsig_runs_dev", (sv.E_INVALID, "c128", _d_runs))
-
-
-def test_unknown_dtype_code(gpu):
-    status, code, call = sv._DTYPE_ENTRIES["vsig_runs_dev"]
-    ctx = gpu.get_context()
-    for bad in (4, -1):
-        rc, _ = call(ctx, bad)
-        assert rc == status, (bad, rc, ctx.lib.vsig_last_error(ctx.h).decode())
-    rc, right = call(ctx, _lib.DTYPES[code])
-    assert rc == _lib.VSIG_OK, (rc, ctx.lib.vsig_last_error(ctx.h).decode())
-    assert right()
 
 
 SENT = -0x0123456789ABCDEF          # fills output buffers before a call

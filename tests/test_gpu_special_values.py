@@ -600,6 +600,14 @@ def _d_peaks(ctx, code):
                         and out.view(torch.float64)[1].item() == _DMAG.max())
 
 
+def _d_runs(ctx, code):
+    x, out, info = _dev(_DX), _zeros(10, torch.int64), _zeros(5, torch.int64)
+    rc = ctx.lib.vsig_runs_dev(ctx.h, code, _ptr(x), 16, 0.0, 0, 0, _ptr(out), 2, _ptr(info))
+    am, mx = int(_DMAG.argmax()), float(_DMAG.max())
+    return rc, lambda: (info[:3].tolist() == [1, 16, am] and out[:3].tolist() == [0, 15, am]
+                        and out.view(torch.float64)[3].item() == mx)
+
+
 def _d_trace(ctx, code):
     x, lo, hi, info = _dev(_DX), _zeros(4, torch.float64), _zeros(4, torch.float64), _zeros(4, torch.int64)
     rc = ctx.lib.vsig_trace_envelope_dev(ctx.h, code, _ptr(x), 16, 0, 0, 16, 4, _lib.TRACE_ABS, 0.0, _ptr(lo),
@@ -707,6 +715,7 @@ def _d_correlate_stats(ctx, code):
 _DTYPE_ENTRIES = {
     "vsig_peak_dev": (E_INVALID, "c128", _d_peak),
     "vsig_peaks_dev": (E_INVALID, "c128", _d_peaks),
+    "vsig_runs_dev": (E_INVALID, "c128", _d_runs),
     "vsig_trace_envelope_dev": (E_INVALID, "c128", _d_trace),
     "vsig_abs_stats_dev": (E_UNSUPPORTED, "c128", _d_abs_stats),
     "vsig_select_dev": (E_INVALID, "f64", _d_select),

@@ -188,6 +188,7 @@ SIGNATURES = {
     "vsig_vector_build_dev": (C.c_int, [P, C.POINTER(PacketPlace), I32, P, I64, P]),
     "vsig_normalize_c64_dev": (C.c_int, [P, P, I64, P, P]),
     "vsig_pfb_c64_dev": (C.c_int, [P, P, I64, P, I32, I32, P, I64]),
+    "vsig_pfb_plan": (C.c_int, [I32, I32, I64, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]),
     "vsig_select_dev": (C.c_int, [P, I32, P, I64, C.POINTER(I64), I32, C.POINTER(C.c_double)]),
     "vsig_threshold_dev": (C.c_int, [P, I32, P, I64, C.c_double, C.POINTER(I64), C.POINTER(I64),
                                      C.POINTER(I64), C.POINTER(C.c_double)]),

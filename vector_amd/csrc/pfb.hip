@@ -222,15 +222,19 @@ __global__ __launch_bounds__(256, (VAR & 4) ? 4 : 1) void pfb_kernel(const float
 // with the non-temporal policy 128 +11 %, 32 +3 %, profiles/r06_pfb_ab.txt).
 constexpr int kPfbVar64 = 7;
 constexpr long long kPfbFramesPerGroup = 64;
+// frames per group: a multiple of the unrolled step, so the (PT-1)-row ring
+// prologue stays a small fraction of the group's reads
+template <class PL, int PT>
+static constexpr long long pfb_fpg() {
+  constexpr int step = PL::E * (PT / cgcd(PL::E, PT));
+  return ((kPfbFramesPerGroup + step - 1) / step) * step;
+}
+
 template <class PL, int PT>
 static void launch_pfb_t(const float2* x, long long n, const float* h, long long M, float2* y,
                          const float2* tw, hipStream_t st) {
-  constexpr int G = 256 / PL::N, E = PL::E;
-  constexpr int step = E * (PT / cgcd(E, PT));
-  // frames per group: a multiple of the unrolled step, so the (PT-1)-row ring
-  // prologue stays a small fraction of the group's reads
-  constexpr long long want = kPfbFramesPerGroup;
-  const long long fpg = ((want + step - 1) / step) * step;
+  constexpr int G = 256 / PL::N;
+  const long long fpg = pfb_fpg<PL, PT>();
   const long long groups = (M + fpg - 1) / fpg;
   const long long blocks = (groups + G - 1) / G;
   hipLaunchKernelGGL((pfb_kernel<PL, PT, PL::N == 64 ? kPfbVar64 : 3>), dim3((unsigned)blocks), dim3(256), 0, st, x, n, h, M,
@@ -253,6 +257,30 @@ hipError_t launch_pfb(int C, int PT, const float2* x, long long n, const float* 
   VSIG_PFB_CASE(128, Plan128)
   VSIG_PFB_CASE(256, Plan256)
 #undef VSIG_PFB_CASE
+  return hipErrorInvalidValue;
+}
+
+// The geometry launch_pfb takes for M frames: frames per group, groups per
+// block and the grid (for vsig_pfb_plan).
+hipError_t pfb_plan(int C, int PT, long long M, long long* fpg, long long* groups_per_block,
+                    long long* blocks) {
+#define VSIG_PFB_PLAN(CC, PL)                                              \
+  if (C == CC) {                                                           \
+    switch (PT) {                                                          \
+      case 4: *fpg = pfb_fpg<PL, 4>(); break;                              \
+      case 8: *fpg = pfb_fpg<PL, 8>(); break;                              \
+      case 16: *fpg = pfb_fpg<PL, 16>(); break;                            \
+      default: return hipErrorInvalidValue;                                \
+    }                                                                      \
+    *groups_per_block = 256 / PL::N;                                       \
+    const long long groups = (M + *fpg - 1) / *fpg;                        \
+    *blocks = (groups + *groups_per_block - 1) / *groups_per_block;        \
+    return hipSuccess;                                                     \
+  }
+  VSIG_PFB_PLAN(64, Plan64)
+  VSIG_PFB_PLAN(128, Plan128)
+  VSIG_PFB_PLAN(256, Plan256)
+#undef VSIG_PFB_PLAN
   return hipErrorInvalidValue;
 }
 

@@ -2009,6 +2009,16 @@ int vsig_pfb_c64_dev(vsig_ctx* c, const void* x, int64_t n, const float* h, int3
   return VSIG_OK;
 }
 
+int vsig_pfb_plan(int32_t nchan, int32_t ntaps, int64_t nframes, int64_t* frames_per_group,
+                  int64_t* groups_per_block, int64_t* blocks) {
+  if (!frames_per_group || !groups_per_block || !blocks || nframes < 1 || nchan < 1 || ntaps % nchan)
+    return VSIG_E_INVALID;
+  long long fpg = 0, gpb = 0, nb = 0;
+  if (vsig::pfb_plan(nchan, ntaps / nchan, nframes, &fpg, &gpb, &nb) != hipSuccess) return VSIG_E_UNSUPPORTED;
+  *frames_per_group = fpg; *groups_per_block = gpb; *blocks = nb;
+  return VSIG_OK;
+}
+
 // ---------------------------------------------------------------- analysis
 // k-th smallest of |a| (0-based ranks) by MSB-first 8-bit radix select:
 // ceil(bits/8) histogram passes over the data, all ranks at once.

@@ -337,6 +337,8 @@ hipError_t launch_channel_direct(int c128, const void* x, long long n, long long
 // pfb.hip: C in {64, 128, 256}, PT in {4, 8, 16}; y frame-major (M x C)
 hipError_t launch_pfb(int C, int PT, const float2* x, long long n, const float* h, long long M,
                       float2* y, const float2* tw, hipStream_t st);
+hipError_t pfb_plan(int C, int PT, long long M, long long* fpg, long long* groups_per_block,
+                    long long* blocks);
 
 // stream_ops.hip
 hipError_t launch_mix_c64(const float2* x, long long n, double w, double sr, long long i0, float2* y,
