@@ -268,7 +268,11 @@ int vsig_fir_c64(vsig_ctx* ctx, const void* x, int64_t n, const float* taps, int
  * c[o] = sum_{k<L} s[o - off + k] conj(p[k]), mode VALID (off = 0, nout = n-L+1)
  * or FULL (off = L-1, nout = n+L-1).  c may be NULL (peak only).  peak_dev: a
  * device vsig_peak (may be NULL); peak = max |c|, sums over all nout outputs;
- * the peak / index are refined (see "refine" above). */
+ * the peak / index are refined (see "refine" above).
+ * Templates of 2049 .. 8192 samples run fastest where s - off is 16-byte
+ * aligned (VALID: s itself; FULL: an odd L): the kernel then loads sample
+ * pairs (parity split); any 8-byte aligned s is accepted and
+ * gives the same record at the float bar. */
 int vsig_xcorr_create(vsig_ctx* ctx, const void* tmpl, int64_t L, vsig_xcorr** out);
 void vsig_xcorr_free(vsig_xcorr* xc);
 int vsig_xcorr_exec_dev(vsig_xcorr* xc, const void* s, int64_t n, int32_t mode, void* c,

@@ -17,8 +17,8 @@
 //             launch for the whole refine): the thread columns whose lane
 //             key is in the band (the outputs m(t) + TF q of one thread, where
 //             the kernel writes lane keys), else the waves whose partial max
-//             is (a wave covers ob + wstep w + l + 64 (q % rsub) + stride
-//             (q / rsub), see xcorr.hip); for a stored c64 array, its
+//             is (a wave covers ob + wstep w + lstep l + rstep (q % rsub) +
+//             stride (q / rsub), see xcorr.hip); for a stored c64 array, its
 //             64-output chunks holding one.  Every item is kept (the scratch
 //             holds all of them) together with the span [lo, hi] of final
 //             outputs the items cover;
@@ -119,7 +119,8 @@ struct RefineGeom {
   int from_array;       // items are 64-output chunks of a stored array
   long long hop;        // partial items: outputs per block, waves per block,
   int waves, Q, stride; //   rows per item and their stride,
-  int wstep, rsub;      //   wave base step, 64-output rows per stride step
+  int wstep, rsub;      //   wave base step, rows per stride step,
+  int lstep, rstep;     //   lane step, step of the rows within a stride step
   int cols;             // > 0: items are thread columns (wave p, column l) =
                         //   p * 64 + l, cols rows each (xcorr_lane_keys)
   int nthr;             // OpenBLAS threads of the numpy being matched (zdotu
@@ -129,7 +130,8 @@ struct RefineGeom {
 };
 
 __device__ __forceinline__ long long row_offset(const RefineGeom& g, int w, int q, int l) {
-  return (long long)g.wstep * w + l + 64LL * (q % g.rsub) + (long long)g.stride * (q / g.rsub);
+  return (long long)g.wstep * w + (long long)g.lstep * l + (long long)g.rstep * (q % g.rsub) +
+         (long long)g.stride * (q / g.rsub);
 }
 
 // Final output of row q, lane l of wave partial p (-1: past the block's outputs).
@@ -185,7 +187,7 @@ __device__ __forceinline__ bool item_span(const RefineGeom& g, long long item, l
   int qh = (g.cols ? g.cols : g.Q) - 1;
   while (row_offset(g, w, qh, l) >= lim) --qh;
   rlo = ob + row_offset(g, w, 0, l);
-  long long top = row_offset(g, w, qh, l) + (g.cols ? 0 : 63);
+  long long top = g.cols ? row_offset(g, w, qh, l) : row_offset(g, w, qh, 63);
   if (top >= lim) top = lim - 1;
   rhi = ob + top;
   if (g.rev) {
@@ -1032,7 +1034,8 @@ __global__ __launch_bounds__(kNpThreads, 2) void refine_fused(
 
 static RefineGeom make_geom(const RefineArgs& r) {
   RefineGeom g{r.nout, r.F, r.na, r.nv, r.rev, r.from_array, r.hop, r.waves, r.Q, r.stride,
-               r.wstep, r.rsub, r.cols, r.blas_threads > 1 ? r.blas_threads : 1, 0, r.cap};
+               r.wstep, r.rsub, r.lstep ? r.lstep : 1, r.rstep ? r.rstep : 64, r.cols,
+               r.blas_threads > 1 ? r.blas_threads : 1, 0, r.cap};
   g.per_item = r.from_array ? 64 : r.cols ? r.cols : (long long)r.Q * 64;
   return g;
 }

@@ -160,6 +160,7 @@ struct vsig_xcorr {
   long long L = 0;
   int M = 0;
   std::vector<DevBuf> Ps;
+  DevBuf SD;        // M = 16384, one spectrum: its parity-split table (xcorr.hip)
   DevBuf tmpl;
   DevBuf cbuf;
   explicit vsig_xcorr(vsig_ctx* c) : ctx(c) {}
@@ -430,7 +431,8 @@ struct RefineOperands {
 // launch finalizes them into rec and selects (thread columns when lkeys).
 int run_refine(vsig_ctx* c, const RefineOperands& op, long long nout, int M, long long hop,
                long long nparts, int rev, const float2* c64, PeakPartial* rec, void* out128,
-               bool fused = false, const unsigned* lkeys = nullptr, bool async = false) {
+               bool fused = false, const unsigned* lkeys = nullptr, bool async = false,
+               bool parity = false) {
   c->refine_ran = false;
   if (!c->refine) return fused ? fail(c, VSIG_E_INVALID, "refine: fused finalize with refine off")
                              : VSIG_OK;
@@ -441,11 +443,13 @@ int run_refine(vsig_ctx* c, const RefineOperands& op, long long nout, int M, lon
     r.from_array = 1; r.c64 = c64; r.Q = 1; r.stride = 0; r.waves = 1; r.hop = 64;
     r.wstep = 64; r.rsub = 1;
   } else {
-    int waves, Q, stride, plan, wstep, rsub;
-    if (vsig::xcorr_geom(M, &waves, &Q, &stride, &plan, &wstep, &rsub) != hipSuccess)
+    vsig::XcorrGeom g;
+    if (vsig::xcorr_geom(M, parity, &g) != hipSuccess)
       return fail(c, VSIG_E_INVALID, "refine: no correlator geometry for M");
+    const int Q = g.Q;
     r.parts = c->parts(); r.nparts = nparts; r.hop = hop;
-    r.waves = waves; r.Q = Q; r.stride = stride; r.wstep = wstep; r.rsub = rsub;
+    r.waves = g.waves; r.Q = g.Q; r.stride = g.stride; r.wstep = g.wstep; r.rsub = g.rsub;
+    r.lstep = g.lstep; r.rstep = g.rstep;
     if (fused) {
       r.finalize = 1;
       r.tmp = c->finalize_tmp();
@@ -1257,6 +1261,10 @@ static int xcorr_build(vsig_ctx* c, const float2* td, long long L, vsig_xcorr* x
     x->Ps.push_back(std::move(P));
     if (L <= Bc) break;
   }
+  if (x->M == 16384 && x->Ps.size() == 1) {     // the parity split's (S, D) table
+    HIPCHK(c, x->SD.alloc((size_t)(x->M / 2) * sizeof(float4)));
+    HIPCHK(c, vsig::launch_xcorr_parity_table(x->M, x->Ps[0].as<float2>(), x->SD.as<float4>(), c->stream));
+  }
   return VSIG_OK;
 }
 
@@ -1278,9 +1286,13 @@ static int xcorr_run(vsig_xcorr* x, const float2* s, long long n, long long off,
     long long hop = (long long)x->M - x->L + 1;
     if (x->M == 16384 && hop > 1) hop &= ~1LL;
     const long long nblocks = (nout + hop - 1) / hop;
-    int waves, Q, stride, plan, wstep, rsub;
-    if (vsig::xcorr_geom(x->M, &waves, &Q, &stride, &plan, &wstep, &rsub) != hipSuccess)
+    // the parity split wherever the segments start 16-byte aligned (else the
+    // split by halves, on the natural-order spectrum)
+    const bool parity = x->M == 16384 && x->SD.data() && !(hop & 1) && vsig::xcorr_parity_aligned(s, off);
+    vsig::XcorrGeom g;
+    if (vsig::xcorr_geom(x->M, parity, &g) != hipSuccess)
       return fail(c, VSIG_E_UNSUPPORTED, "correlator block size");
+    const int waves = g.waves, Q = g.Q, plan = g.plan;
     const long long nparts = nblocks * waves;   // one partial per wave
     int rc = ensure_partials(c, nparts);
     if (rc) return rc;
@@ -1300,7 +1312,8 @@ static int xcorr_run(vsig_xcorr* x, const float2* s, long long n, long long off,
     {
       Timed t(c, "xcorr");
       HIPCHK(c, vsig::launch_xcorr_os(x->M, s, n, x->Ps[0].as<float2>(), off, nout, hop, cout, store_mode,
-                                      c->parts(), tw, wt, c->stream, lk));
+                                      c->parts(), tw, wt, c->stream, lk,
+                                      parity ? x->SD.as<float4>() : nullptr));
     }
     if (!fused) {
       if ((rc = finalize_peak(c, nparts, 1, peak_dev))) return rc;
@@ -1308,7 +1321,7 @@ static int xcorr_run(vsig_xcorr* x, const float2* s, long long n, long long off,
     }
     if (out128 && cout) HIPCHK(c, vsig::launch_convert_c(1, cout, nout, out128, c->stream));
     return run_refine(c, *op, nout, x->M, hop, nparts, (store_mode & 4) ? 1 : 0, nullptr, rec, out128,
-                      fused, lk, async && peak_dev != nullptr);
+                      fused, lk, async && peak_dev != nullptr, parity);
   }
   constexpr long long B = 8192;
   constexpr int M = 16384;
@@ -1319,10 +1332,10 @@ static int xcorr_run(vsig_xcorr* x, const float2* s, long long n, long long off,
     cbuf = x->cbuf.as<float2>();
   }
   const float2 *tw, *wt;
-  int waves, Q, stride, plan, wstep, rsub;
-  if (vsig::xcorr_geom(M, &waves, &Q, &stride, &plan, &wstep, &rsub) != hipSuccess)
+  vsig::XcorrGeom g;
+  if (vsig::xcorr_geom(M, false, &g) != hipSuccess)
     return fail(c, VSIG_E_UNSUPPORTED, "correlator block size");
-  if ((rc = get_twiddles(c, plan, &tw)) || (rc = get_half_tw(c, M, 512, &wt))) return rc;
+  if ((rc = get_twiddles(c, g.plan, &tw)) || (rc = get_half_tw(c, M, 512, &wt))) return rc;
   {
     Timed t(c, "xcorr");            // the whole chunked correlation + its peak pass
     for (size_t p = 0; p < x->Ps.size(); ++p) {

@@ -178,18 +178,26 @@ hipError_t launch_fir_os(int M, const float2* x, long long n, long long g0, cons
                          int ntaps, long long hop, int decim, float2* y, const float2* tw,
                          hipStream_t st, const MixArgs* mix = nullptr);
 // Correlator, M in {4096, 8192, 16384} (16384: half-frame kernel, tw = the
-// 8192-point table, wt = W_M^t for t < 512).
+// 8192-point table, wt = W_M^t for t < 512).  SD (M = 16384, hop even,
+// xcorr_parity_aligned(s, off)): the template's parity-split table
+// (launch_xcorr_parity_table of Ps); the launch then splits its frames by
+// sample parity (16-byte segment loads, xcorr_geom's parity geometry).
 hipError_t launch_xcorr_os(int M, const float2* s, long long n, const float2* Ps, long long off,
                            long long nout, long long hop, float2* c, int store_mode,
                            PeakPartial* partials, const float2* tw, const float2* wt,
-                           hipStream_t st, unsigned* lkeys = nullptr);
+                           hipStream_t st, unsigned* lkeys = nullptr, const float4* SD = nullptr);
+hipError_t launch_xcorr_parity_table(int M, const float2* Ps, float4* SD, hipStream_t st);
+bool xcorr_parity_aligned(const float2* s, long long off);
 // Rows per thread column if the correlator for M can write lane keys
 // (lkeys[b TF + m(t)]: thread t's max |c|^2 key, the refine's column
 // candidates), else 0.
 int xcorr_lane_keys(int M);
 // Outputs of wave w of block b of the correlator for M (the refine pass's
-// items): ob + wstep w + l + 64 (q % rsub) + stride (q / rsub), l < 64, q < Q.
-hipError_t xcorr_geom(int M, int* waves, int* Q, int* stride, int* plan, int* wstep, int* rsub);
+// items): ob + wstep w + lstep l + rstep (q % rsub) + stride (q / rsub),
+// l < 64, q < Q; plan: the twiddle table's key.  parity: the M = 16384 launch
+// with its (S, D) table.
+struct XcorrGeom { int waves, Q, stride, plan, wstep, rsub, lstep, rstep; };
+hipError_t xcorr_geom(int M, bool parity, XcorrGeom* g);
 // xcorr_bank.hip: K templates of one length against one stream, M in {4096,
 // 8192, 16384}.  Ps: K spectra of M points; c: K rows of nout (may be null);
 // partials[(k nblocks + b) waves + wave], nblocks = ceil(nout / hop), with
@@ -231,8 +239,9 @@ struct RefineArgs {
   const float2* c64;
   const PeakPartial* parts;         // or from the fused correlator's wave partials
   long long nparts, hop;
-  int waves, Q, stride;             // wave w of block b: ob + wstep w + l + 64 (q % rsub)
-  int wstep, rsub;                  //   + stride (q / rsub), l < 64, q < Q (xcorr_geom)
+  int waves, Q, stride;             // wave w of block b: ob + wstep w + lstep l + rstep
+  int wstep, rsub;                  //   (q % rsub) + stride (q / rsub), l < 64, q < Q
+  int lstep, rstep;                 //   (xcorr_geom; 0: the plain map's 1 and 64)
   double eps;                       // fp32 candidate band (relative)
   int blas_threads;                 // OpenBLAS threads of the numpy matched (sums > 10000)
   int cols;                         // > 0: thread-column items from lane keys (Q = 1;

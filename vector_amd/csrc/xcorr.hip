@@ -1,7 +1,8 @@
 // Cross-correlation kernels (gfx950): overlap-save correlation with the fused
 // |c|^2 argmax / sums epilogue (correlate, find_correlation_peak).
 //   M = 16384 (templates of 2049 .. 8192 samples): xcorr_half_kernel, two
-//     8192-point halves through LDS, two blocks per CU;
+//     8192-point halves through LDS, two blocks per CU; split by sample
+//     parity (PS) where the segments start 16-byte aligned, else by half;
 //   M = 32768 (8193 .. 16384): the same with 16384-point halves;
 //   M = 4096 / 8192 (templates up to 1024 / 2048): xcorr_os_kernel, one frame
 //     per block, persistent with the next segment prefetched.
@@ -20,7 +21,8 @@ namespace vsig {
 // sum of template chunks).
 // Partials: one per wave.  Wave w of block b covers the outputs
 //   b*hop + 64 w + l + TF q,   l < 64, q < Q   (Q = E, or 2 E for the half
-// kernel), which refine.hip uses to revisit a wave's outputs (xcorr_geom).
+// kernel; the parity split: b*hop + 128 w + 2 l + (q % 2) + 2 TF (q / 2)),
+// which refine.hip uses to revisit a wave's outputs (xcorr_geom).
 // ---------------------------------------------------------------------------
 // Persistent: a block walks blocks b, b + grid, ...; the next segment is
 // loaded behind the (L2-resident) template-spectrum loads, so it lands while
@@ -117,6 +119,56 @@ __device__ __forceinline__ void load_halves(float2* a, float2* d, const float2* 
       d[e] = (x1 >= 0 && x1 < n) ? base[i + H] : make_float2(0.f, 0.f);
     }
   }
+}
+
+// The parity split's operands: a[e] = x[2 i], d[e] = x[2 i + 1], i =
+// in_index(t, e), one 16-byte load per element (half the load instructions
+// of load_halves for the same lines); s0 must leave x + s0 16-byte aligned
+// (xcorr_parity_aligned).  Edge blocks: the same elements, bounds-checked.
+template <class P>
+__device__ __forceinline__ void load_parity(float2* a, float2* d, const float2* __restrict__ x,
+                                            long long s0, long long n, int t) {
+  constexpr int H = P::N;
+  const float2* base = x + s0;
+  if (s0 >= 0 && s0 + 2 * H <= n) {
+    const auto rs = make_rsrc(base, 2u * H * (unsigned)sizeof(float2));
+    const unsigned v0 = (unsigned)in_index<P>(t, 0) * (unsigned)sizeof(float4);
+    static_for<0, P::E>([&](auto ei) {
+      constexpr int e = decltype(ei)::value;
+      const float4 q = buf_load4(rs, v0, in_off<P>(e) * (int)sizeof(float4));
+      a[e] = make_float2(q.x, q.y);
+      d[e] = make_float2(q.z, q.w);
+    });
+  } else {
+#pragma unroll
+    for (int e = 0; e < P::E; ++e) {
+      const int i = 2 * in_index<P>(t, e);
+      const long long x0 = s0 + i, x1 = x0 + 1;
+      a[e] = (x0 >= 0 && x0 < n) ? base[i] : make_float2(0.f, 0.f);
+      d[e] = (x1 >= 0 && x1 < n) ? base[i + 1] : make_float2(0.f, 0.f);
+    }
+  }
+}
+
+// out_index(t, e) = m(t) + out_off(e): the parity split's frequency-side
+// twiddle W_N^out_index = W_N^m(t) * W_64^parity_root(e) (roots of the lower
+// half circle as minus their opposite: twc holds 32).
+template <class P>
+constexpr int parity_root(int e) { return out_off<P>(e) / (P::N / 64); }
+
+// acc + a * b and acc - a * b (cmul's two halves, the second with its signs
+// turned)
+__device__ __forceinline__ float2 cmac(float2 a, float2 b, float2 acc) {
+  const f2v av = tov(a), bv = tov(b);
+  return cmul_fin(a, b, av * bv.xx + tov(acc));
+}
+__device__ __forceinline__ float2 cmsub(float2 a, float2 b, float2 acc) {
+  const f2v av = tov(a), bv = tov(b);
+  const f2v t = tov(acc) - av * bv.xx;
+  f2v r;
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]"
+      : "=v"(r) : "v"(av), "v"(bv), "v"(t));
+  return fromv(r);
 }
 
 // A thread's outputs out_index(t, e) = m(t) + c_e (+ H for the second half)
@@ -289,6 +341,100 @@ __device__ __forceinline__ void xcorr_half_epilogue(const float2* a, const float
   wave_partial_f(m, mi, s1, s2, rev, ob, nout, partials + b * (P::TF / 64) + (t >> 6));
 }
 
+// Epilogue of a parity-split block: a[e] holds output 2 i, d[e] output 2 i + 1,
+// i = out_index(t, e) = m(t) + kStep rank(e).  A thread's outputs rise with
+// 2 rank + parity, which is the key's 6 low bits (< 64): the first-maximum and
+// rev rules are xcorr_half_epilogue's.
+// DV >= 0: the launch's interior blocks (lim == hop = 2 DV kStep) keep exactly
+// the ranks below DV of both a and d, at compile time; other blocks, and
+// DV < 0, split at run time: rank r is whole when 2 kStep (r + 1) <= lim,
+// absent when 2 kStep r >= lim (wave-uniform), and only the straddling rank
+// takes the per-lane mask.
+template <class P, int DV = -1>
+__device__ __forceinline__ void xcorr_parity_epilogue(const float2* a, const float2* d,
+                                                      long long b, long long hop, long long nout,
+                                                      float2* __restrict__ c, int store_mode,
+                                                      PeakPartial* partials, unsigned* lkeys,
+                                                      int t) {
+  using KR = KeyedRank<P>;
+  static_assert(KR::ok && KR::kStep == P::TF, "the parity split keys by 2 rank + parity");
+  const long long ob = b * hop;
+  const long long rem = nout - ob;
+  const int lim = rem < hop ? (int)rem : (int)hop;
+  const bool rev = store_mode & 4;
+  const bool accum = store_mode & 8;
+  const int smode = store_mode & 3;
+  if (smode == 1) {
+#pragma unroll
+    for (int e = 0; e < P::E; ++e) {
+      const int i = 2 * out_index<P>(t, e);
+      if (i < lim) put_c(c + ob + (unsigned)i, cconj(a[e]), accum);
+      if (i + 1 < lim) put_c(c + ob + (unsigned)(i + 1), cconj(d[e]), accum);
+    }
+  } else if (smode == 2) {
+#pragma unroll
+    for (int e = 0; e < P::E; ++e) {
+      const int i = 2 * out_index<P>(t, e);
+      if (i < lim) put_c(c + (nout - 1 - ob) - i, a[e], accum);
+      if (i + 1 < lim) put_c(c + (nout - 1 - ob) - (i + 1), d[e], accum);
+    }
+  }
+  if (!partials) return;
+  auto keyed = [&](auto revc) {
+    constexpr bool kRev = decltype(revc)::value;
+    constexpr unsigned rx = kRev ? 0u : 63u;
+    unsigned key = 0u;
+    bool any = false;
+    float s1 = 0.f, s2 = 0.f;
+    auto acc = [&](float2 v, int i, int k6, auto masked) {
+      const float a2 = v.x * v.x + v.y * v.y;
+      const unsigned k = (__float_as_uint(a2) & ~63u) | ((unsigned)k6 ^ rx);
+      if constexpr (decltype(masked)::value) {
+        const bool ok = i < lim;
+        key = ok ? (k > key ? k : key) : key;
+        any |= ok;
+        s1 += ok ? __builtin_amdgcn_sqrtf(a2) : 0.f;
+        s2 += ok ? a2 : 0.f;
+      } else {
+        key = k > key ? k : key;
+        any = true;
+        s1 += __builtin_amdgcn_sqrtf(a2);
+        s2 += a2;
+      }
+    };
+    if (DV >= 0 && lim == hop) {       // interior block, compile-time split
+      static_for<0, P::E>([&](auto ei) {
+        constexpr int e = decltype(ei)::value;
+        if constexpr (KR::rank(e) < DV) {
+          acc(a[e], 0, 2 * KR::rank(e), IC<0>{});
+          acc(d[e], 0, 2 * KR::rank(e) + 1, IC<0>{});
+        }
+      });
+    } else {
+      static_for<0, P::E>([&](auto ei) {
+        constexpr int e = decltype(ei)::value;
+        constexpr int c0 = 2 * KR::kStep * KR::rank(e);
+        if (c0 + 2 * KR::kStep <= lim) {
+          acc(a[e], 0, 2 * KR::rank(e), IC<0>{});
+          acc(d[e], 0, 2 * KR::rank(e) + 1, IC<0>{});
+        } else if (c0 < lim) {
+          const int i = 2 * out_index<P>(t, e);
+          acc(a[e], i, 2 * KR::rank(e), IC<1>{});
+          acc(d[e], i + 1, 2 * KR::rank(e) + 1, IC<1>{});
+        }
+      });
+    }
+    // lane keys (refine candidates per thread column, see xcorr_lane_keys)
+    if (lkeys) lkeys[b * P::TF + tmapl<P>(t)] = key;
+    const int k6 = (int)((key & 63u) ^ rx);
+    const int mi = 2 * (tmapl<P>(t) + KR::kStep * (k6 >> 1)) + (k6 & 1);
+    const float m = any ? __uint_as_float(key & ~63u) : -1.f;
+    wave_partial_f(m, mi, s1, s2, kRev, ob, nout, partials + b * (P::TF / 64) + (t >> 6));
+  };
+  if (rev) keyed(IC<1>{});
+  else keyed(IC<0>{});
+}
+
 // waves per SIMD: 16-value plans (Plan8192w) two 512-thread blocks per CU =
 // 4; 32-value plans two 256-thread blocks (2) or one 512-thread block (1)
 template <class P>
@@ -309,7 +455,24 @@ constexpr int xcorr_waves_per_eu() { return P::E <= 16 ? 4 : P::TF >= 512 ? 1 : 
 // 48 +5 %, a prefetch of the block's own segment (no look-ahead) +6.7 %.
 constexpr int kSegPfDist = 64;
 
-template <class P, int DV = -1>
+// PS: the M-point transforms split by sample parity instead of by half:
+//   a = x[2 i], d = x[2 i + 1] (load_parity)  ->  E, O = FFT_H(a), FFT_H(d),
+//   X[k] = E[k] + w^k O[k],  X[k + H] = E[k] - w^k O[k]       (w = W_M, k < H)
+// and the second transform takes Z = conj(X) P as low and high halves,
+//   r[2 m] = FFT_H(Z[k] + Z[k + H]),  r[2 m + 1] = FFT_H((Z[k] - Z[k + H]) w^k),
+// so both radix-2 steps sit on the frequency side and fold into the product:
+//   U = conj(E) S + conj(O) D,   V = conj(E) D W_H^k + conj(O) S,
+//   S = P[k] + P[k + H],  D = (P[k] - P[k + H]) conj(w^k)     (xcorr_parity_table:
+// Ps2[k] = (S, D), the bytes of the (even bin, odd bin) table).  W_H^k =
+// W_H^m(t) (wt[2 m(t)], the one per-thread twiddle) times a compile-time 64th
+// root (parity_root).  No time-side work at all: a[e] / d[e] come out as
+// outputs 2 i / 2 i + 1, i = out_index(t, e) (xcorr_parity_epilogue).
+// 12 packed ops per element pair around the transforms instead of 17 and half
+// the segment-load instructions: 2.09-2.10 against 2.20-2.21 ms at config 5
+// (3534 against 3671 VALU per wave, 220 VGPRs; profiles/r07_xcorr_parity_ab.txt).
+// A third table D W_H^k (no per-element twiddle, one more load per element
+// pair) measured 3 % slower there.
+template <class P, int DV = -1, bool PS = false>
 __global__ __launch_bounds__(P::TF, xcorr_waves_per_eu<P>()) void xcorr_half_kernel(
     const float2* __restrict__ s, long long n, const float4* __restrict__ Ps2, long long off,
     long long nout, long long hop, float2* __restrict__ c, int store_mode,
@@ -338,19 +501,22 @@ __global__ __launch_bounds__(P::TF, xcorr_waves_per_eu<P>()) void xcorr_half_ker
   };
   // W_M^base: base = in_index(t, 0), loaded ahead of the segment and the
   // prefetch below (loads complete in issue order)
-  const float2 w = wt[in_index<P>(t, 0)];
+  const float2 w = wt[PS ? 2 * out_index<P>(t, 0) : in_index<P>(t, 0)];
   float2 a[P::E], d[P::E];
-  load_halves<P>(a, d, s, b * hop - off, n, t);
+  if constexpr (PS) load_parity<P>(a, d, s, b * hop - off, n, t);
+  else load_halves<P>(a, d, s, b * hop - off, n, t);
   constexpr int kPfLines = 2 * P::N * 8 / 128 / P::TF;          // 128-byte lines per thread
   float pfv[kPfLines];
 #pragma unroll
   for (int k = 0; k < kPfLines; ++k) pfv[k] = 0.f;
-  static_for<0, P::E>([&](auto ei) {
-    constexpr int e = decltype(ei)::value;
-    const float2 x0 = a[e], x1 = d[e];
-    a[e] = cadd(x0, x1);
-    d[e] = twc<half_root<P, M>(e), 64>(cmul(csub(x0, x1), w));
-  });
+  if constexpr (!PS) {
+    static_for<0, P::E>([&](auto ei) {
+      constexpr int e = decltype(ei)::value;
+      const float2 x0 = a[e], x1 = d[e];
+      a[e] = cadd(x0, x1);
+      d[e] = twc<half_root<P, M>(e), 64>(cmul(csub(x0, x1), w));
+    });
+  }
   fft2(a, d);
   {
     const auto rp = make_rsrc(Ps2, (unsigned)P::N * (unsigned)sizeof(float4));
@@ -360,18 +526,30 @@ __global__ __launch_bounds__(P::TF, xcorr_waves_per_eu<P>()) void xcorr_half_ker
       const float4 p = buf_load4(rp, v0, out_off<P>(e) * (int)sizeof(float4));
       // (conj folded into the product's neg modifiers: fewer instructions,
       // but +4 % at config 5 in both its forms, profiles/r06_conj_std_ab.txt)
-      a[e] = cmul(cconj(a[e]), make_float2(p.x, p.y));
-      d[e] = cmul(cconj(d[e]), make_float2(p.z, p.w));
+      if constexpr (PS) {
+        const float2 S = make_float2(p.x, p.y), D = make_float2(p.z, p.w);
+        constexpr int K = parity_root<P>(e);
+        const float2 Dw = twc<K % 32, 64>(cmul(D, w));       // K >= 32: -D W_H^k
+        const float2 ce = cconj(a[e]), co = cconj(d[e]);
+        a[e] = cmac(co, D, cmul(ce, S));
+        if constexpr (K < 32) d[e] = cmac(ce, Dw, cmul(co, S));
+        else d[e] = cmsub(ce, Dw, cmul(co, S));
+      } else {
+        a[e] = cmul(cconj(a[e]), make_float2(p.x, p.y));
+        d[e] = cmul(cconj(d[e]), make_float2(p.z, p.w));
+      }
     });
   }
   fft2(a, d);
-  static_for<0, P::E>([&](auto ei) {
-    constexpr int e = decltype(ei)::value;
-    const float2 o = twc<half_root<P, M>(e), 64>(cmul(d[e], w));
-    const float2 ev = a[e];
-    a[e] = cadd(ev, o);
-    d[e] = csub(ev, o);
-  });
+  if constexpr (!PS) {
+    static_for<0, P::E>([&](auto ei) {
+      constexpr int e = decltype(ei)::value;
+      const float2 o = twc<half_root<P, M>(e), 64>(cmul(d[e], w));
+      const float2 ev = a[e];
+      a[e] = cadd(ev, o);
+      d[e] = csub(ev, o);
+    });
+  }
   {                                          // the segment prefetch (kSegPfDist)
     const long long bn = b + kSegPfDist;
     const long long s0 = bn * hop - off;
@@ -381,36 +559,71 @@ __global__ __launch_bounds__(P::TF, xcorr_waves_per_eu<P>()) void xcorr_half_ker
       for (int k = 0; k < kPfLines; ++k) pfv[k] = q[(t + k * P::TF) * 32];
     }
   }
-  xcorr_half_epilogue<P, DV>(a, d, b, hop, nout, c, store_mode, partials, lkeys, t);
+  if constexpr (PS) xcorr_parity_epilogue<P, DV>(a, d, b, hop, nout, c, store_mode, partials, lkeys, t);
+  else xcorr_half_epilogue<P, DV>(a, d, b, hop, nout, c, store_mode, partials, lkeys, t);
 #pragma unroll
   for (int k = 0; k < kPfLines; ++k)   // the prefetch loads stay; their values are never used
     asm volatile("" ::"v"(pfv[k]));
   cs.done(clk);
 }
 
+// (S, D) of the parity split from the M-point template spectrum P (natural
+// order), in double: SD[k] = (P[k] + P[k + H], (P[k] - P[k + H]) conj(W_M^k)).
+__global__ __launch_bounds__(256) void xcorr_parity_table_kernel(const float2* __restrict__ P,
+                                                                 float4* __restrict__ SD, int H) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= H) return;
+  const float2 p0 = P[k], p1 = P[k + H];
+  const double dr = (double)p0.x - (double)p1.x, di = (double)p0.y - (double)p1.y;
+  double sn, cs;
+  sincospi((double)k / (double)H, &sn, &cs);        // conj(W_M^k) = exp(+i pi k / H)
+  SD[k] = make_float4((float)((double)p0.x + (double)p1.x), (float)((double)p0.y + (double)p1.y),
+                      (float)(dr * cs - di * sn), (float)(dr * sn + di * cs));
+}
+
+hipError_t launch_xcorr_parity_table(int M, const float2* Ps, float4* SD, hipStream_t st) {
+  if (M != 16384) return hipErrorInvalidValue;
+  const int H = M / 2;
+  hipLaunchKernelGGL(xcorr_parity_table_kernel, dim3((H + 255) / 256), dim3(256), 0, st, Ps, SD, H);
+  return hipGetLastError();
+}
+
+// Every segment start s + b hop - off of an M = 16384 launch (hop even) is
+// 16-byte aligned: the parity split's loads.
+bool xcorr_parity_aligned(const float2* s, long long off) {
+  return (((long long)(reinterpret_cast<unsigned long long>(s) >> 3) - off) & 1) == 0;
+}
+
 hipError_t launch_xcorr_os(int M, const float2* s, long long n, const float2* Ps, long long off,
                            long long nout, long long hop, float2* c, int store_mode,
                            PeakPartial* partials, const float2* tw, const float2* wt,
-                           hipStream_t st, unsigned* lkeys) {
+                           hipStream_t st, unsigned* lkeys, const float4* SD) {
   if (nout <= 0) return hipSuccess;
   if (lkeys && !xcorr_lane_keys(M)) return hipErrorInvalidValue;
+  if (SD && (M != 16384 || (hop & 1) || (reinterpret_cast<unsigned long long>(s) & 7) ||
+             !xcorr_parity_aligned(s, off)))
+    return hipErrorInvalidValue;
   const long long nblocks = (nout + hop - 1) / hop;
   if (M == 16384) {
-    // interior blocks keep the second half's ranks below (hop - H) / kStep: the
-    // common split (hop = 12288: L = 4096, 4097) has its compile-time epilogue
+    // interior blocks keep the second half's ranks below (hop - H) / kStep (the
+    // parity split: the ranks below hop / (2 kStep) of both halves): the common
+    // split (hop = 12288: L = 4096, 4097) has its compile-time epilogue
     using KR = KeyedRank<PlanX16k>;
     constexpr int kDv = PlanX16k::E / 2;
+    constexpr int kDvPs = (PlanX16k::N + kDv * KR::kStep) / (2 * KR::kStep);
     const long long cut = hop - PlanX16k::N;
     const bool dv = KR::ok && KR::kStep == PlanX16k::TF && cut == (long long)kDv * KR::kStep;
-    if (dv) {
-      hipLaunchKernelGGL((xcorr_half_kernel<PlanX16k, kDv>), dim3((unsigned)nblocks),
-                         dim3(PlanX16k::TF), 0, st, s, n, reinterpret_cast<const float4*>(Ps), off, nout,
-                         hop, c, store_mode, partials, nblocks, tw, wt, lkeys, g_clock_sink);
-      return hipGetLastError();
+    auto run = [&](auto kern, const float4* tab) {
+      hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(PlanX16k::TF), 0, st, s, n, tab, off,
+                         nout, hop, c, store_mode, partials, nblocks, tw, wt, lkeys, g_clock_sink);
+    };
+    if (SD) {
+      if (dv) run(xcorr_half_kernel<PlanX16k, kDvPs, true>, SD);
+      else run(xcorr_half_kernel<PlanX16k, -1, true>, SD);
+    } else {
+      if (dv) run(xcorr_half_kernel<PlanX16k, kDv>, reinterpret_cast<const float4*>(Ps));
+      else run(xcorr_half_kernel<PlanX16k>, reinterpret_cast<const float4*>(Ps));
     }
-    hipLaunchKernelGGL(xcorr_half_kernel<PlanX16k>, dim3((unsigned)nblocks), dim3(PlanX16k::TF), 0,
-                       st, s, n, reinterpret_cast<const float4*>(Ps), off, nout, hop, c, store_mode,
-                       partials, nblocks, tw, wt, lkeys, g_clock_sink);
     return hipGetLastError();
   }
   if (M == 32768) {     // 16384-point halves, one block per CU
@@ -437,7 +650,8 @@ hipError_t launch_xcorr_os(int M, const float2* s, long long n, const float2* Ps
 // m(t) = its last-pass butterfly base, which is column m(t) mod 64 of wave
 // m(t) / 64 in xcorr_geom's terms), else 0.
 // The column's outputs m(t) + kStep R (R < 2E) are xcorr_geom's rows q = R
-// when kStep is the row stride TF.
+// when kStep is the row stride TF (the parity split: the outputs 2 (m(t) +
+// kStep (R / 2)) + R % 2, the rows of xcorr_geom's parity geometry).
 template <class P>
 constexpr int lane_key_rows() {
   return KeyedRank<P>::ok && KeyedRank<P>::kStep == P::TF && 2 * P::E <= 64 ? 2 * P::E : 0;
@@ -450,15 +664,20 @@ int xcorr_lane_keys(int M) {
 
 // Wave geometry of the correlator's partials (see the header comment):
 // waves per block, rows Q and their stride; twiddle plan size.
-hipError_t xcorr_geom(int M, int* waves, int* Q, int* stride, int* plan, int* wstep, int* rsub) {
-  *wstep = 64;
-  *rsub = 1;
-  if (M == 32768) { *waves = PlanX32k::TF / 64; *Q = 2 * PlanX32k::E; *stride = PlanX32k::TF; *plan = -16384; }
+// The parity split (M = 16384 launched with its (S, D) table): thread m(t) =
+// 64 w + l holds the outputs 2 m(t) + (q % 2) + 2 TF (q / 2), q = 2 rank +
+// parity < 2 E -- wave step 128, lane step 2, two rows one output apart per
+// stride 2 TF.
+hipError_t xcorr_geom(int M, bool parity, XcorrGeom* g) {
+  g->wstep = 64; g->rsub = 1; g->lstep = 1; g->rstep = 64;
+  if (parity && M != 16384) return hipErrorInvalidValue;
+  if (M == 32768) { g->waves = PlanX32k::TF / 64; g->Q = 2 * PlanX32k::E; g->stride = PlanX32k::TF; g->plan = -16384; }
   else if (M == 16384) {
-    *waves = PlanX16k::TF / 64; *Q = 2 * PlanX16k::E; *stride = PlanX16k::TF; *plan = kPlanKey16k;
+    g->waves = PlanX16k::TF / 64; g->Q = 2 * PlanX16k::E; g->stride = PlanX16k::TF; g->plan = kPlanKey16k;
+    if (parity) { g->wstep = 128; g->lstep = 2; g->rsub = 2; g->rstep = 1; g->stride = 2 * PlanX16k::TF; }
   }
-  else if (M == 8192) { *waves = Plan8192::TF / 64; *Q = Plan8192::E; *stride = Plan8192::TF; *plan = 8192; }
-  else if (M == 4096) { *waves = Plan4096::TF / 64; *Q = Plan4096::E; *stride = Plan4096::TF; *plan = 4096; }
+  else if (M == 8192) { g->waves = Plan8192::TF / 64; g->Q = Plan8192::E; g->stride = Plan8192::TF; g->plan = 8192; }
+  else if (M == 4096) { g->waves = Plan4096::TF / 64; g->Q = Plan4096::E; g->stride = Plan4096::TF; g->plan = 4096; }
   else return hipErrorInvalidValue;
   return hipSuccess;
 }
