@@ -237,6 +237,87 @@ int vsig_psd_traces_c64(vsig_ctx* ctx, const void* x, int64_t n, const float* wi
 int vsig_psd_traces_plan(int32_t nfft, int64_t nframes, int64_t* blocks, int64_t* frames_per_block_step,
                          int64_t* frames_per_block);
 
+/* ---- segmented spectrum traces: vsig_psd_traces_c64_dev's three detectors for every
+ * segment of a table, in one pass over all their frames (per-burst spectra: the table is
+ * what vsig_runs lists).  window (float32[nperseg]), hop, nfft >= nperseg, scale and shift
+ * are vsig_psd_c64_dev's; stride is 1.  Table: nseg entries {start, len} in samples with
+ * 0 <= start, len >= 0, start + len <= n; segments may touch, overlap, repeat and come in
+ * any order.  Segment s has nframes[s] = (len - nperseg) / hop + 1 frames if
+ * len >= nperseg, else 0; its frame m covers x[start + m*hop + i], i < nperseg, and
+ * P[s][m][k] is the float32 value vsig_psd_c64_dev stores for that frame (the same
+ * expression on the same transform).  Row-major outputs, one row of nfft bins a segment:
+ *   mean[s][k] = (sum over m of (double)P[s][m][k]) / nframes[s]    float64[nseg][nfft]
+ *   max[s][k], min[s][k]: np.max / np.min over m (a NaN stays)      float32[nseg][nfft]
+ * A NaN P makes that bin NaN in all three outputs of every segment whose frames hold it
+ * and of no other; a segment with no frame gets NaN in its whole row of every output.
+ * Samples outside the union of the frames (between segments, past a segment's last whole
+ * frame, in a segment shorter than nperseg) are not read.
+ * nfft: the powers of two from 64 to 8192; any other is VSIG_E_UNSUPPORTED.
+ * vsig_psd_segments_create validates everything, takes the table from the HOST, builds
+ *   the block table (a block owns a contiguous run of at most max_run_frames frames of
+ *   one segment, transformed frames_per_step at a time; runs are sized so that the blocks
+ *   fill the device once, and to at least four steps) and uploads it; it allocates the
+ *   plan's own scratch (16 bytes x nfft per block) and may synchronise.
+ *   VSIG_E_INVALID, with a message that names the offending segment where there is one:
+ *   nseg < 0 or > 2^24, n < 1 or > 2^40, a segment outside [0, n], hop < 1, nperseg < 1,
+ *   nfft < nperseg, a NULL ctx / out, a NULL table with nseg > 0.  nseg == 0 is valid.
+ * vsig_psd_segments_run takes DEVICE pointers: x (complex64[n], 8-byte aligned), win,
+ *   and the outputs, any of which may be NULL (not computed; all three NULL, a NULL x or
+ *   win, or a misaligned x: VSIG_E_INVALID before any work is enqueued).  It enqueues on
+ *   the context stream, allocates nothing, never synchronises and can be captured into a
+ *   graph; a plan with nseg == 0 does nothing.  It reads 8 bytes per frame sample and
+ *   writes O(nseg * nfft).  No float atomics; the launch geometry is a function of
+ *   (nfft, the table, the device) alone, so the same input gives the same bytes on every
+ *   run, and by vsig_psd_traces_c64_dev's argument max and min do not depend on the
+ *   geometry at all and the mean by about nframes * 2^-53 relative.
+ * vsig_psd_segments_info: the plan's frames (all segments), blocks, frames per step and
+ *   the longest run a block is given.
+ * vsig_psd_segments_free waits for the context stream, then frees the plan. */
+typedef struct vsig_segment_t { int64_t start, len; } vsig_segment_t;
+typedef struct vsig_psd_segments vsig_psd_segments;
+int vsig_psd_segments_create(vsig_ctx* ctx, const vsig_segment_t* segs /*host*/, int64_t nseg, int64_t n,
+                             int32_t nperseg, int64_t hop, int32_t nfft, vsig_psd_segments** out);
+void vsig_psd_segments_free(vsig_psd_segments* plan);
+int vsig_psd_segments_info(const vsig_psd_segments* plan, int64_t* frames_total, int64_t* blocks,
+                           int64_t* frames_per_step, int64_t* max_run_frames);
+int vsig_psd_segments_run(vsig_psd_segments* plan, const void* x, const float* win, float scale,
+                          int32_t shift, double* mean, float* max, float* min);
+
+/* ---- band measurement: where the power of each of nrows spectra sits.  rows: DEVICE
+ * float64, row r at rows + r*ld, nbins <= ld values M[k] >= 0 in ascending frequency
+ * (vsig_psd_segments_run's mean with shift = 1; any non-negative rows).  Per row, in
+ * double, with c[k] the inclusive cumulative sum of M in ascending k:
+ *   power    = total = c[nbins-1]
+ *   peak_bin = the first maximum, peak = its value
+ *   centroid = (sum of k * M[k]) / total, a fractional bin
+ *   lo_bin   = the smallest k with c[k] >= tail * total
+ *   hi_bin   = the smallest k with c[k] >= (1 - tail) * total
+ * so [lo_bin, hi_bin] holds the fraction 1 - 2 tail of the power (the occupied bandwidth).
+ * A row that holds a NaN (flags bit 0) or whose total is not > 0 (flags bit 1): power =
+ * the total as summed, centroid = peak = NaN, peak_bin = lo_bin = hi_bin = -1.
+ * The sums run in a fixed order that is not np.cumsum's left-to-right one (contiguous
+ * chunks of 16 bins, each summed ascending; the chunk sums in a fixed tree): the same
+ * input gives the same bytes on every run, and every c[k] and the total are within
+ * nbins * 2^-52 * total of the sequential sums -- the indices are those of the sequential
+ * sum whenever none of its values lies that close to a target.  lo_bin / hi_bin are the
+ * first k at which the c so formed reaches the target (nbins-1 for a target within that
+ * rounding of the total).
+ * out: DEVICE vsig_band_t[nrows].  The call enqueues on the context stream, allocates
+ * nothing and never synchronises (capturable).  VSIG_E_INVALID before any work is
+ * enqueued: nrows < 0 or >= 2^31, nbins < 1, ld < nbins, a tail outside (0, 0.5) or NaN,
+ * a NULL ctx / rows / out, rows or out not 8-byte aligned.  nrows == 0 does nothing. */
+typedef struct vsig_band_t {
+  double power;      /* sum of the row */
+  double centroid;   /* power-weighted mean bin */
+  double peak;       /* the largest value */
+  int32_t peak_bin;  /* its first bin */
+  int32_t lo_bin;    /* first bin at which the cumulative sum reaches tail * power */
+  int32_t hi_bin;    /* ... (1 - tail) * power */
+  int32_t flags;     /* bit 0: a NaN in the row; bit 1: power not > 0 */
+} vsig_band_t;
+int vsig_band_measure_run(vsig_ctx* ctx, const double* rows, int64_t nrows, int32_t nbins, int64_t ld,
+                          double tail, vsig_band_t* out);
+
 /* ---- FIR: y[g] = sum_{m<ntaps} h[m] x[g*decim - m] (x = 0 outside [0, n)),
  * g in [0, ceil(n/decim)).  Taps complex64 on the host (real taps: imag = 0);
  * any ntaps >= 1 (np.convolve's contract, utils.py:802,816): up to 8192 one

@@ -118,6 +118,17 @@ class TraceInfo(C.Structure):
 TRACE_ABS, TRACE_DB20 = 0, 1
 
 
+class Segment(C.Structure):
+    """vsig_segment_t (include/vsig.h)."""
+    _fields_ = [("start", I64), ("len", I64)]
+
+
+class Band(C.Structure):
+    """vsig_band_t (include/vsig.h)."""
+    _fields_ = [("power", C.c_double), ("centroid", C.c_double), ("peak", C.c_double),
+                ("peak_bin", I32), ("lo_bin", I32), ("hi_bin", I32), ("flags", I32)]
+
+
 # name -> (restype, argtypes); every symbol include/vsig.h declares.
 SIGNATURES = {
     "vsig_version": (C.c_int, []),
@@ -145,6 +156,11 @@ SIGNATURES = {
     "vsig_psd_traces_c64_dev": (C.c_int, [P, P, I64, I64, P, I32, I64, I32, F32, I32, I64, P, P, P]),
     "vsig_psd_traces_c64": (C.c_int, [P, P, I64, P, I32, I64, I32, F32, I32, I64, P, P, P]),
     "vsig_psd_traces_plan": (C.c_int, [I32, I64, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]),
+    "vsig_psd_segments_create": (C.c_int, [P, C.POINTER(Segment), I64, I64, I32, I64, I32, C.POINTER(P)]),
+    "vsig_psd_segments_free": (None, [P]),
+    "vsig_psd_segments_info": (C.c_int, [P, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]),
+    "vsig_psd_segments_run": (C.c_int, [P, P, P, F32, I32, P, P, P]),
+    "vsig_band_measure_run": (C.c_int, [P, P, I64, I32, I64, C.c_double, P]),
     "vsig_fir_create": (C.c_int, [P, P, I32, I32, C.POINTER(P)]),
     "vsig_fir_free": (None, [P]),
     "vsig_fir_exec_dev": (C.c_int, [P, P, I64, P, I64]),

@@ -168,6 +168,19 @@ struct vsig_xcorr {
   ~vsig_xcorr() { (void)hipStreamSynchronize(ctx->stream); }
 };
 
+// The tables and record rows of one segment table (vsig_psd_segments_create).
+struct vsig_psd_segments {
+  vsig_ctx* ctx;
+  long long nseg = 0, n = 0, hop = 0;
+  int nperseg = 0, nfft = 0;
+  long long frames_total = 0, nblocks = 0, step = 0, run = 0, max_rows = 0;
+  const float2* tw = nullptr;      // the context's cached table
+  DevBuf blocks, segs, rows;
+  explicit vsig_psd_segments(vsig_ctx* c) : ctx(c) {}
+  // the stream may still use the tables: wait, then the members free them
+  ~vsig_psd_segments() { (void)hipStreamSynchronize(ctx->stream); }
+};
+
 // A bank of K templates of one length L <= kBankMaxL: the K spectra of M
 // points in one table (row k at Ps + k M).
 constexpr long long kBankMaxL = 4096;
@@ -1090,6 +1103,122 @@ int vsig_psd_traces_c64(vsig_ctx* c, const void* x, int64_t n, const float* win,
   if (max) HIPCHK(c, hipMemcpyAsync(max, dx, bf, hipMemcpyDeviceToHost, c->stream));
   if (min) HIPCHK(c, hipMemcpyAsync(min, dn, bf, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VSIG_OK;
+}
+
+// ---------------------------------------------------------------- segmented spectrum traces
+int vsig_psd_segments_create(vsig_ctx* c, const vsig_segment_t* segs, int64_t nseg, int64_t n, int32_t nperseg,
+                             int64_t hop, int32_t nfft, vsig_psd_segments** out) {
+  if (!c || !out) return fail(c, VSIG_E_INVALID, "null pointer");
+  *out = nullptr;
+  if (nseg < 0 || nseg > (1LL << 24)) return fail(c, VSIG_E_INVALID, "nseg must be in [0, 2^24]");
+  if (nseg > 0 && !segs) return fail(c, VSIG_E_INVALID, "null segment table");
+  if (n < 1 || n > (1LL << 40)) return fail(c, VSIG_E_INVALID, "n must be in [1, 2^40]");
+  if (nperseg < 1 || hop < 1) return fail(c, VSIG_E_INVALID, "need nperseg >= 1 and hop >= 1");
+  if (nfft < nperseg) return fail(c, VSIG_E_INVALID, "nfft must be >= nperseg");
+  for (long long s = 0; s < nseg; ++s) {
+    const long long st = segs[s].start, ln = segs[s].len;
+    if (st < 0 || ln < 0 || st > n || ln > n - st)
+      return fail(c, VSIG_E_INVALID, "segment " + std::to_string(s) + " {start " + std::to_string(st) + ", len " +
+                                         std::to_string(ln) + "} is outside [0, " + std::to_string(n) + "]");
+  }
+  if (!vsig::psd_traces_in_lds(nfft))
+    return fail(c, VSIG_E_UNSUPPORTED, "segmented traces: nfft " + std::to_string(nfft) +
+                                           " is not a power of two in [64, 8192]");
+  int step = 0;
+  long long maxb = 0;
+  if (vsig::psd_segments_geom(nfft, &step, &maxb) != hipSuccess) return fail(c, VSIG_E_UNSUPPORTED, "no plan");
+  std::unique_ptr<vsig_psd_segments> p(new vsig_psd_segments(c));
+  p->nseg = nseg; p->n = n; p->nperseg = nperseg; p->hop = hop; p->nfft = nfft; p->step = step;
+  // runs of `run` frames: enough steps per block that the blocks fill the
+  // device once, and kTracesMinUnits at least; a segment's blocks (its record
+  // rows) are consecutive
+  std::vector<vsig::PsdSegRows> rows((size_t)nseg);
+  long long units = 0;
+  for (long long s = 0; s < nseg; ++s) {
+    const long long nf = segs[s].len >= nperseg ? (segs[s].len - nperseg) / hop + 1 : 0;
+    rows[s].nframes = nf;
+    p->frames_total += nf;
+    units += (nf + step - 1) / step;
+  }
+  long long upb = (units + maxb - 1) / maxb;
+  if (upb < vsig::kTracesMinUnits) upb = vsig::kTracesMinUnits;
+  p->run = upb * step;
+  std::vector<vsig::PsdSegBlock> blocks;
+  for (long long s = 0; s < nseg; ++s) {
+    rows[s].r0 = (long long)blocks.size();
+    for (long long f0 = 0; f0 < rows[s].nframes; f0 += p->run) {
+      const long long left = rows[s].nframes - f0;
+      blocks.push_back({segs[s].start + f0 * hop, left < p->run ? left : p->run});
+    }
+    rows[s].r1 = (long long)blocks.size();
+    if (rows[s].r1 - rows[s].r0 > p->max_rows) p->max_rows = rows[s].r1 - rows[s].r0;
+  }
+  p->nblocks = (long long)blocks.size();
+  if (p->nblocks > 0x7fffffffLL) return fail(c, VSIG_E_UNSUPPORTED, "more than 2^31 - 1 blocks");
+  if (nseg > 0) {
+    bool two_level;
+    const int key = vsig::psd_traces_table(nfft, &two_level);
+    int rc;
+    if ((rc = two_level ? get_tw2(c, key, &p->tw) : get_twiddles(c, key, &p->tw))) return rc;
+    HIPCHK(c, p->segs.alloc(rows.size() * sizeof(vsig::PsdSegRows)));
+    HIPCHK(c, hipMemcpyAsync(p->segs.data(), rows.data(), rows.size() * sizeof(vsig::PsdSegRows),
+                             hipMemcpyHostToDevice, c->stream));
+    if (p->nblocks > 0) {
+      HIPCHK(c, p->blocks.alloc(blocks.size() * sizeof(vsig::PsdSegBlock)));
+      HIPCHK(c, hipMemcpyAsync(p->blocks.data(), blocks.data(), blocks.size() * sizeof(vsig::PsdSegBlock),
+                               hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, p->rows.alloc((size_t)p->nblocks * (size_t)nfft * sizeof(vsig::PsdRec)));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // the host tables go out of scope
+  }
+  *out = p.release();
+  return VSIG_OK;
+}
+
+void vsig_psd_segments_free(vsig_psd_segments* p) { delete p; }
+
+int vsig_psd_segments_info(const vsig_psd_segments* p, int64_t* frames_total, int64_t* blocks,
+                           int64_t* frames_per_step, int64_t* max_run_frames) {
+  if (!p) return VSIG_E_INVALID;
+  if (!frames_total || !blocks || !frames_per_step || !max_run_frames)
+    return fail(p->ctx, VSIG_E_INVALID, "null pointer");
+  *frames_total = p->frames_total; *blocks = p->nblocks; *frames_per_step = p->step; *max_run_frames = p->run;
+  return VSIG_OK;
+}
+
+int vsig_psd_segments_run(vsig_psd_segments* p, const void* x, const float* win, float scale, int32_t shift,
+                          double* mean, float* max, float* min) {
+  if (!p) return VSIG_E_INVALID;
+  vsig_ctx* c = p->ctx;
+  if (!x || !win) return fail(c, VSIG_E_INVALID, "null pointer");
+  if (!mean && !max && !min) return fail(c, VSIG_E_INVALID, "no output asked for");
+  if (reinterpret_cast<uintptr_t>(x) & 7) return fail(c, VSIG_E_INVALID, "x must be 8-byte aligned");
+  if (p->nseg == 0) return VSIG_OK;
+  Timed t(c, "psd_segments");
+  if (p->nblocks > 0)
+    HIPCHK(c, vsig::launch_psd_segments(p->nfft, (const float2*)x, win, p->nperseg, p->hop, scale, shift ? 1 : 0,
+                                        p->tw, p->blocks.as<vsig::PsdSegBlock>(), p->nblocks,
+                                        p->rows.as<vsig::PsdRec>(), c->stream));
+  HIPCHK(c, vsig::launch_psd_segments_merge(p->rows.as<vsig::PsdRec>(), p->segs.as<vsig::PsdSegRows>(), p->nseg,
+                                            p->nfft, p->max_rows, mean, max, min, c->stream));
+  return VSIG_OK;
+}
+
+int vsig_band_measure_run(vsig_ctx* c, const double* rows, int64_t nrows, int32_t nbins, int64_t ld, double tail,
+                          vsig_band_t* out) {
+  static_assert(sizeof(vsig_band_t) == sizeof(vsig::BandRec) && sizeof(vsig_band_t) == 40, "vsig_band_t");
+  if (!c) return VSIG_E_INVALID;
+  if (nrows < 0 || nrows > 0x7fffffffLL) return fail(c, VSIG_E_INVALID, "nrows must be in [0, 2^31)");
+  if (nbins < 1 || ld < nbins) return fail(c, VSIG_E_INVALID, "need nbins >= 1 and ld >= nbins");
+  if (!(tail > 0.0 && tail < 0.5)) return fail(c, VSIG_E_INVALID, "tail must be inside (0, 0.5)");
+  if (!rows || !out) return fail(c, VSIG_E_INVALID, "null pointer");
+  if ((reinterpret_cast<uintptr_t>(rows) & 7) || (reinterpret_cast<uintptr_t>(out) & 7))
+    return fail(c, VSIG_E_INVALID, "rows and out must be 8-byte aligned");
+  if (nrows == 0) return VSIG_OK;
+  Timed t(c, "band_measure");
+  HIPCHK(c, vsig::launch_band_measure(rows, nrows, nbins, ld, tail, reinterpret_cast<vsig::BandRec*>(out),
+                                      c->stream));
   return VSIG_OK;
 }
 

@@ -145,6 +145,7 @@ struct PsdRec { double sum; float mx, mn; };
 // are folded into kPsdFoldRows rows, frames interleaved (step 1, fpb 0).
 struct PsdTracesPlan { long long blocks, step, fpb; };
 constexpr int kPsdFoldRows = 8;
+constexpr int kTracesMinUnits = 4;           // steps a block runs at least (when there are that many)
 bool psd_traces_in_lds(long long N);
 PsdTracesPlan psd_traces_plan(long long N, long long nframes);
 // The twiddle table launch_psd_traces reads for N: its plan key (plan_info's
@@ -161,6 +162,25 @@ hipError_t launch_psd_traces_fold(const float* sxx, long long nb, long long N, i
 // rows[nrows][N] -> mean (sum / nframes), max, min; any output may be null
 hipError_t launch_psd_traces_merge(const PsdRec* rows, long long nrows, long long N, long long nframes,
                                    double* mean, float* mx, float* mn, hipStream_t st);
+// psd_segments.hip: the traces of every segment of a table in one launch
+// (vsig_psd_segments_run; see the file's header).  Block b transforms the
+// `nframes` frames that start at sample x0 (hop apart) into record row b;
+// segment s folds its rows [r0, r1) and divides by its nframes (0: a NaN row).
+struct PsdSegBlock { long long x0, nframes; };
+struct PsdSegRows { long long r0, r1, nframes; };
+// (frames per step, blocks the device holds at once: CUs x resident blocks) of the segmented kernel for N
+hipError_t psd_segments_geom(int N, int* step, long long* max_blocks);
+// rows: nblocks * N records; tw: psd_traces_table(N)'s
+hipError_t launch_psd_segments(int N, const float2* x, const float* win, int nperseg, long long hop,
+                               float scale, int shift, const float2* tw, const PsdSegBlock* blocks,
+                               long long nblocks, PsdRec* rows, hipStream_t st);
+// max_rows: the most rows [r0, r1) any segment has (it picks the block size)
+hipError_t launch_psd_segments_merge(const PsdRec* rows, const PsdSegRows* segs, long long nseg, int N,
+                                     long long max_rows, double* mean, float* mx, float* mn, hipStream_t st);
+// vsig_band_t (include/vsig.h) of every row of rows[nrows][ld], nbins used
+struct BandRec { double power, centroid, peak; int peak_bin, lo_bin, hi_bin, flags; };
+hipError_t launch_band_measure(const double* rows, long long nrows, int nbins, long long ld, double tail,
+                               BandRec* out, hipStream_t st);
 // Decimating FIR in the frequency domain (M = 1024, D = 2 / 4; see fir.hip).
 // mix != nullptr: the mixer above applied to every loaded sample (fused).
 hipError_t launch_fir_dec(int decim, const float2* x, long long n, long long g0, const float2* Hs,
