@@ -318,6 +318,63 @@ typedef struct vsig_band_t {
 int vsig_band_measure_run(vsig_ctx* ctx, const double* rows, int64_t nrows, int32_t nbins, int64_t ld,
                           double tail, vsig_band_t* out);
 
+/* ---- burst isolation: every segment of a table mixed down to baseband and band-filtered,
+ * all segments in one launch (the inverse of what vsig_vector_build_dev assembles; the
+ * table is what vsig_runs lists, the frequencies what vsig_band_measure_run finds).
+ * x: the capture, complex64[n]; sr the sample rate; T = ntaps, odd, d = (T-1)/2.  Segment
+ * s = {start, len, freq, filter} covers the capture indices [lo, hi) = [start, start+len)
+ * with 0 <= lo < hi <= n and uses row `filter` of the taps (real float32, F rows of T):
+ *   u_s[i] = x[i] * exp(-2j*pi*freq*i/sr)              phase origin = capture index 0
+ *   z_s[j] = sum_{m<T} h[m] * u_s[lo + j + d - m],  j in [0, len),  u_s = 0 outside [0, n)
+ * i.e. the whole capture mixed by -freq, a linear-phase filter with its group delay
+ * removed ("same" alignment), then the slice: the filter sees the capture's own samples
+ * on both sides of the segment, zeros only beyond the capture's ends, and overlapping or
+ * repeated segments of one frequency agree sample for sample.  The phase is formed as
+ * theta = (w/sr)*i with w = -2*pi*freq, reduced in double, rotated in fp32 (the fused
+ * mixer's form, vsig_fir_exec_mix_dev); freq == 0 is not rotated at all.  The packed
+ * output y holds z_0, z_1, ... back to back: z_s starts at offsets[s], offsets the prefix
+ * sums of len.  Segments may touch, overlap, repeat and come in any order.
+ * Work runs in 1024-point overlap-save frames of hop = 1025 - T outputs, each segment
+ * cut into ceil(len / hop) frames of its own (two frames a workgroup, which may belong to
+ * different segments and filters); a frame reads x[g + d - (T-1) .. + 1024) for its first
+ * output's capture index g, clipped to [0, n).
+ * Non-finite input: a NaN or Inf sample makes every output of every frame whose window
+ * holds it non-finite and changes no bit of any other frame's outputs.
+ * ntaps: odd, 3 .. 511 (hop 1022 .. 514); an odd ntaps above 511 is VSIG_E_UNSUPPORTED.
+ * vsig_isolate_create validates everything, takes the table and the taps from the HOST,
+ *   builds the F x 1024 filter spectra and the frame table (32 bytes a frame) on the
+ *   device and may synchronise.  VSIG_E_INVALID, with a message that names the offending
+ *   segment where there is one: nseg < 0 or > 2^24, n < 1 or > 2^40, a segment with
+ *   len < 1 or outside [0, n), a filter index outside [0, nfilters), a non-finite freq,
+ *   nfilters outside [1, 4096], an even ntaps or one below 3, sr not finite or not > 0, a
+ *   non-finite tap, a NULL ctx / out / taps, a NULL table with nseg > 0.  nseg == 0 is valid.
+ * vsig_isolate_info: the packed output's length, the frames, the workgroups, the hop.
+ * vsig_isolate_offsets: the nseg + 1 prefix sums into a HOST array.
+ * vsig_isolate_run takes DEVICE pointers: x (complex64[n]) and y (complex64[out_total]),
+ *   both 8-byte aligned, not overlapping (a NULL or misaligned pointer: VSIG_E_INVALID
+ *   before any work is enqueued).  It enqueues on the context stream, allocates nothing,
+ *   never synchronises and can be captured into a graph; a plan with nseg == 0 does
+ *   nothing.  x is read inside [0, n) only, y written at [0, out_total) exactly, each
+ *   element once.  No atomics; the grid is a function of the table alone, so the same
+ *   input gives the same bytes on every run.
+ * vsig_isolate_free waits for the context stream, then frees the plan. */
+typedef struct vsig_isolate_seg_t {
+  int64_t start;    /* first capture index of the output range */
+  int64_t len;      /* outputs */
+  double freq;      /* the centre mixed down to 0, Hz (same unit as sr) */
+  int32_t filter;   /* row of taps */
+  int32_t pad;
+} vsig_isolate_seg_t;
+typedef struct vsig_isolate vsig_isolate;
+int vsig_isolate_create(vsig_ctx* ctx, const vsig_isolate_seg_t* segs /*host*/, int64_t nseg, int64_t n,
+                        const float* taps /*host float[nfilters*ntaps]*/, int32_t nfilters, int32_t ntaps,
+                        double sr, vsig_isolate** out);
+void vsig_isolate_free(vsig_isolate* plan);
+int vsig_isolate_info(const vsig_isolate* plan, int64_t* out_total, int64_t* frames, int64_t* blocks,
+                      int64_t* hop);
+int vsig_isolate_offsets(const vsig_isolate* plan, int64_t* offsets /*host, nseg + 1*/);
+int vsig_isolate_run(vsig_isolate* plan, const void* x, void* y);
+
 /* ---- FIR: y[g] = sum_{m<ntaps} h[m] x[g*decim - m] (x = 0 outside [0, n)),
  * g in [0, ceil(n/decim)).  Taps complex64 on the host (real taps: imag = 0);
  * any ntaps >= 1 (np.convolve's contract, utils.py:802,816): up to 8192 one

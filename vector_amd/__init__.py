@@ -28,6 +28,7 @@ from .analysis import (Packets, boxcar_energy, detect_packet_bounds, detect_pack
 from .display import (SpectrogramImage, colormap_table, image_extent, plot_spectrogram_image,  # noqa: F401
                       pool_factors, spectrogram_image, spectrogram_levels)
 from .traces import Trace, averaged_spectrum_trace, capture_spectrum, signal_envelope, trace_bin  # noqa: F401
-from .packets import PacketMeasurements, SegmentSpectra, measure_packets, segment_spectra  # noqa: F401
+from .packets import (IsolatedPackets, PacketMeasurements, SegmentSpectra, design_lowpass,  # noqa: F401
+                      isolate_packets, measure_packets, segment_spectra)
 
 __version__ = "0.1.0"

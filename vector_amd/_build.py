@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvsig.so")
-SOURCES = ["psd.hip", "psd_traces.hip", "psd_segments.hip", "fir.hip", "xcorr.hip", "xcorr_bank.hip", "reduce.hip", "refine.hip", "bigfft.hip", "analysis.hip", "pfb.hip",
+SOURCES = ["psd.hip", "psd_traces.hip", "psd_segments.hip", "fir.hip", "isolate.hip", "xcorr.hip", "xcorr_bank.hip", "reduce.hip", "refine.hip", "bigfft.hip", "analysis.hip", "pfb.hip",
            "stream_ops.hip", "vector_build.hip", "peaks.hip", "runs.hip", "region.hip", "display.hip", "trace.hip", "chain.hip",
            "vsig_api.hip"]
 HEADERS = ["fft_engine.hpp", "os_common.hpp", "vsig_kernels.h", "npabs.hpp", "dtype.hpp", "dbmath.hpp", "xcorr_epilogue.hpp", "psd_traces_run.hpp"]

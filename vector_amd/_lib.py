@@ -129,6 +129,11 @@ class Band(C.Structure):
                 ("peak_bin", I32), ("lo_bin", I32), ("hi_bin", I32), ("flags", I32)]
 
 
+class IsolateSeg(C.Structure):
+    """vsig_isolate_seg_t (include/vsig.h)."""
+    _fields_ = [("start", I64), ("len", I64), ("freq", C.c_double), ("filter", I32), ("pad", I32)]
+
+
 # name -> (restype, argtypes); every symbol include/vsig.h declares.
 SIGNATURES = {
     "vsig_version": (C.c_int, []),
@@ -161,6 +166,12 @@ SIGNATURES = {
     "vsig_psd_segments_info": (C.c_int, [P, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]),
     "vsig_psd_segments_run": (C.c_int, [P, P, P, F32, I32, P, P, P]),
     "vsig_band_measure_run": (C.c_int, [P, P, I64, I32, I64, C.c_double, P]),
+    "vsig_isolate_create": (C.c_int, [P, C.POINTER(IsolateSeg), I64, I64, C.POINTER(F32), I32, I32, C.c_double,
+                                      C.POINTER(P)]),
+    "vsig_isolate_free": (None, [P]),
+    "vsig_isolate_info": (C.c_int, [P, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]),
+    "vsig_isolate_offsets": (C.c_int, [P, C.POINTER(I64)]),
+    "vsig_isolate_run": (C.c_int, [P, P, P]),
     "vsig_fir_create": (C.c_int, [P, P, I32, I32, C.POINTER(P)]),
     "vsig_fir_free": (None, [P]),
     "vsig_fir_exec_dev": (C.c_int, [P, P, I64, P, I64]),

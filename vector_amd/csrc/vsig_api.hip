@@ -181,6 +181,20 @@ struct vsig_psd_segments {
   ~vsig_psd_segments() { (void)hipStreamSynchronize(ctx->stream); }
 };
 
+// The frame table and filter spectra of one burst table (vsig_isolate_create).
+constexpr int kIsoMaxTaps = 511, kIsoMaxFilters = 4096;
+struct vsig_isolate {
+  vsig_ctx* ctx;
+  long long nseg = 0, n = 0, nframes = 0, hop = 0;
+  int lo = 0;                      // circular index of a frame's first output (ntaps - 1)
+  std::vector<long long> offsets;  // nseg + 1 prefix sums of the packed output
+  const float2* tw = nullptr;      // the context's cached table
+  DevBuf frames, Hs;
+  explicit vsig_isolate(vsig_ctx* c) : ctx(c) {}
+  // the stream may still use the tables: wait, then the members free them
+  ~vsig_isolate() { (void)hipStreamSynchronize(ctx->stream); }
+};
+
 // A bank of K templates of one length L <= kBankMaxL: the K spectra of M
 // points in one table (row k at Ps + k M).
 constexpr long long kBankMaxL = 4096;
@@ -1219,6 +1233,108 @@ int vsig_band_measure_run(vsig_ctx* c, const double* rows, int64_t nrows, int32_
   Timed t(c, "band_measure");
   HIPCHK(c, vsig::launch_band_measure(rows, nrows, nbins, ld, tail, reinterpret_cast<vsig::BandRec*>(out),
                                       c->stream));
+  return VSIG_OK;
+}
+
+// ---------------------------------------------------------------- burst isolation
+int vsig_isolate_create(vsig_ctx* c, const vsig_isolate_seg_t* segs, int64_t nseg, int64_t n, const float* taps,
+                        int32_t nfilters, int32_t ntaps, double sr, vsig_isolate** out) {
+  static_assert(sizeof(vsig_isolate_seg_t) == 32 && sizeof(vsig::IsoFrame) == 32, "table records");
+  constexpr int M = vsig::kIsoM;
+  if (!c || !out) return fail(c, VSIG_E_INVALID, "null pointer");
+  *out = nullptr;
+  if (nseg < 0 || nseg > (1LL << 24)) return fail(c, VSIG_E_INVALID, "nseg must be in [0, 2^24]");
+  if (nseg > 0 && !segs) return fail(c, VSIG_E_INVALID, "null segment table");
+  if (n < 1 || n > (1LL << 40)) return fail(c, VSIG_E_INVALID, "n must be in [1, 2^40]");
+  if (!taps) return fail(c, VSIG_E_INVALID, "null taps");
+  if (nfilters < 1 || nfilters > kIsoMaxFilters)
+    return fail(c, VSIG_E_INVALID, "nfilters must be in [1, " + std::to_string(kIsoMaxFilters) + "]");
+  if (ntaps < 3 || ntaps % 2 == 0) return fail(c, VSIG_E_INVALID, "ntaps must be odd and >= 3");
+  if (ntaps > kIsoMaxTaps)
+    return fail(c, VSIG_E_UNSUPPORTED, "isolate: ntaps " + std::to_string(ntaps) + " is above " +
+                                           std::to_string(kIsoMaxTaps));
+  if (!(sr > 0.0) || !std::isfinite(sr)) return fail(c, VSIG_E_INVALID, "sr must be finite and > 0");
+  for (long long i = 0; i < (long long)nfilters * ntaps; ++i)
+    if (!std::isfinite(taps[i])) return fail(c, VSIG_E_INVALID, "tap " + std::to_string(i) + " is not finite");
+  for (long long s = 0; s < nseg; ++s) {
+    const long long st = segs[s].start, ln = segs[s].len;
+    if (st < 0 || ln < 1 || st >= n || ln > n - st)
+      return fail(c, VSIG_E_INVALID, "segment " + std::to_string(s) + " {start " + std::to_string(st) + ", len " +
+                                         std::to_string(ln) + "} is empty or outside [0, " + std::to_string(n) + ")");
+    if (segs[s].filter < 0 || segs[s].filter >= nfilters)
+      return fail(c, VSIG_E_INVALID, "segment " + std::to_string(s) + ": filter " + std::to_string(segs[s].filter) +
+                                         " is outside [0, " + std::to_string(nfilters) + ")");
+    if (!std::isfinite(segs[s].freq))
+      return fail(c, VSIG_E_INVALID, "segment " + std::to_string(s) + ": freq is not finite");
+  }
+  std::unique_ptr<vsig_isolate> p(new vsig_isolate(c));
+  p->nseg = nseg; p->n = n; p->lo = ntaps - 1; p->hop = M - p->lo;
+  const long long d = (ntaps - 1) / 2;
+  // segment s: frames k < ceil(len / hop), frame k owns the outputs [k hop, k hop + keep)
+  p->offsets.assign((size_t)nseg + 1, 0);
+  std::vector<vsig::IsoFrame> frames;
+  for (long long s = 0; s < nseg; ++s) {
+    const double wsr = (2.0 * M_PI) * -segs[s].freq / sr;       // vsig_fir_exec_mix_dev's w / sr
+    for (long long o = 0; o < segs[s].len; o += p->hop) {
+      const long long left = segs[s].len - o;
+      frames.push_back({segs[s].start + o + d - p->lo, p->offsets[s] + o, wsr,
+                        (int)(left < p->hop ? left : p->hop), segs[s].filter});
+    }
+    p->offsets[s + 1] = p->offsets[s] + segs[s].len;
+  }
+  p->nframes = (long long)frames.size();
+  if ((p->nframes + 1) / 2 > 0x7fffffffLL) return fail(c, VSIG_E_UNSUPPORTED, "more than 2^31 - 1 blocks");
+  if (nseg > 0) {
+    int rc;
+    const float2* twp;
+    if ((rc = get_twiddles(c, -M, &p->tw)) || (rc = get_twiddles(c, M, &twp))) return rc;
+    // Hs row f = FFT_M(h_f) / M, as vsig_fir_create builds its one
+    std::vector<float2> hc((size_t)nfilters * ntaps);
+    for (size_t i = 0; i < hc.size(); ++i) hc[i] = make_float2(taps[i], 0.f);
+    DevBuf hd;                     // the taps on the device, dropped on return
+    HIPCHK(c, hd.alloc(hc.size() * sizeof(float2)));
+    HIPCHK(c, p->Hs.alloc((size_t)nfilters * M * sizeof(float2)));
+    HIPCHK(c, p->frames.alloc(frames.size() * sizeof(vsig::IsoFrame)));
+    HIPCHK(c, hipMemcpyAsync(hd.data(), hc.data(), hc.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p->frames.data(), frames.data(), frames.size() * sizeof(vsig::IsoFrame),
+                             hipMemcpyHostToDevice, c->stream));
+    hipError_t e = hipSuccess;
+    for (int f = 0; f < nfilters && e == hipSuccess; ++f)
+      e = vsig::launch_spectrum_prep(M, hd.as<float2>() + (size_t)f * ntaps, ntaps, 1.0f / (float)M,
+                                     p->Hs.as<float2>() + (size_t)f * M, twp, c->stream);
+    (void)hipStreamSynchronize(c->stream);           // hd and the host tables go out of scope
+    if (e != hipSuccess) return fail(c, VSIG_E_HIP, hipGetErrorString(e));
+  }
+  *out = p.release();
+  return VSIG_OK;
+}
+
+void vsig_isolate_free(vsig_isolate* p) { delete p; }
+
+int vsig_isolate_info(const vsig_isolate* p, int64_t* out_total, int64_t* frames, int64_t* blocks, int64_t* hop) {
+  if (!p) return VSIG_E_INVALID;
+  if (!out_total || !frames || !blocks || !hop) return fail(p->ctx, VSIG_E_INVALID, "null pointer");
+  *out_total = p->offsets.back(); *frames = p->nframes; *blocks = (p->nframes + 1) / 2; *hop = p->hop;
+  return VSIG_OK;
+}
+
+int vsig_isolate_offsets(const vsig_isolate* p, int64_t* offsets) {
+  if (!p) return VSIG_E_INVALID;
+  if (!offsets) return fail(p->ctx, VSIG_E_INVALID, "null pointer");
+  for (size_t s = 0; s < p->offsets.size(); ++s) offsets[s] = p->offsets[s];
+  return VSIG_OK;
+}
+
+int vsig_isolate_run(vsig_isolate* p, const void* x, void* y) {
+  if (!p) return VSIG_E_INVALID;
+  vsig_ctx* c = p->ctx;
+  if (!x || !y) return fail(c, VSIG_E_INVALID, "null pointer");
+  if ((reinterpret_cast<uintptr_t>(x) & 7) || (reinterpret_cast<uintptr_t>(y) & 7))
+    return fail(c, VSIG_E_INVALID, "x and y must be 8-byte aligned");
+  if (p->nseg == 0) return VSIG_OK;
+  Timed t(c, "isolate");
+  HIPCHK(c, vsig::launch_isolate((const float2*)x, p->n, p->Hs.as<float2>(), p->lo, (float2*)y,
+                                 p->frames.as<vsig::IsoFrame>(), p->nframes, p->tw, c->stream));
   return VSIG_OK;
 }
 

@@ -181,6 +181,17 @@ hipError_t launch_psd_segments_merge(const PsdRec* rows, const PsdSegRows* segs,
 struct BandRec { double power, centroid, peak; int peak_bin, lo_bin, hi_bin, flags; };
 hipError_t launch_band_measure(const double* rows, long long nrows, int nbins, long long ld, double tail,
                                BandRec* out, hipStream_t st);
+// isolate.hip: every segment of a table mixed down and band-filtered in one
+// launch (vsig_isolate_run; see the file's header).  One record per 1024-point
+// overlap-save frame: its input window starts at capture index x0 (zero fill
+// outside [0, n)), its `keep` outputs (circular indices [lo, lo + keep)) go to
+// y + y0, multiplied by row `filter` of Hs (F x kIsoM, FFT(h) / kIsoM) after
+// the mixer exp(j wsr i) on capture index i.
+constexpr int kIsoM = 1024;
+struct IsoFrame { long long x0, y0; double wsr; int keep, filter; };
+// tw: the one-wave 1024-point plan's table (plan key -1024)
+hipError_t launch_isolate(const float2* x, long long n, const float2* Hs, int lo, float2* y,
+                          const IsoFrame* frames, long long nframes, const float2* tw, hipStream_t st);
 // Decimating FIR in the frequency domain (M = 1024, D = 2 / 4; see fir.hip).
 // mix != nullptr: the mixer above applied to every loaded sample (fused).
 hipError_t launch_fir_dec(int decim, const float2* x, long long n, long long g0, const float2* Hs,
