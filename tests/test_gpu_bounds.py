@@ -11,7 +11,7 @@ family is the one of its parity test, named where it is applied.
 Block sizes come from the library's queries (vsig_fir_block,
 vsig_xcorr_bank_plan, vsig_psd_traces_plan, vsig_pfb_plan, vsig_peaks_tile,
 vsig_runs_tile).  One geometry has no query: the single-template correlator's
-block, which _xc_plan restates from the rule in vsig_api.hip (the block is
+block, which _xc_plan restates from the rule in api_xcorr.hip (the block is
 fixed by the template length; the hop is even at 16384 points).
 
 Every entry point is held to the bit-identical read bound.  The detector
@@ -702,7 +702,7 @@ XC_L_STREAM = XC_L + [17_000]               # over 16384: one pass per 8192-samp
 
 def _xc_plan(L):
     """(M, [hop, ...]) of the single-template correlator.  The library has no
-    query for it, so this restates the rule of vsig_api.hip (os_size_xcorr and
+    query for it, so this restates the rule of api_xcorr.hip (os_size_xcorr and
     xcorr_run): M = 4096 up to L = 1024, 8192 up to 2048, 16384 up to 8192,
     32768 up to 16384; hop = M - L + 1 outputs per block, rounded down to even
     at M = 16384.  Longer templates run one M = 16384 pass per 8192-sample

@@ -1,4 +1,4 @@
-"""Teardown of the C-ABI layer's device memory (vsig_api.hip: DevBuf): contexts
+"""Teardown of the C-ABI layer's device memory (vsig_ctx.hpp: DevBuf): contexts
 and handles are created, driven through every large scratch family and freed,
 over and over, and the device's free memory must not sink.
 

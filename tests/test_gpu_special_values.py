@@ -567,7 +567,7 @@ def test_c4_stored_correlation_contains_a_non_finite_sample(gpu):
 
 # =========================================================================== D
 # An unknown dtype code at every *_dev entry point that takes one: the status
-# vsig_api.hip gives it (most refuse it themselves; vsig_db_dev and the two
+# the C-ABI layer gives it (most refuse it themselves; vsig_db_dev and the two
 # abs entry points hand it to their launcher, whose hipErrorInvalidValue comes
 # back as VSIG_E_HIP), and the context goes on working.
 E_INVALID, E_HIP, E_UNSUPPORTED = -1, -2, -4

@@ -17,8 +17,12 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvsig.so")
 SOURCES = ["psd.hip", "psd_traces.hip", "psd_segments.hip", "fir.hip", "isolate.hip", "xcorr.hip", "xcorr_bank.hip", "reduce.hip", "refine.hip", "bigfft.hip", "analysis.hip", "pfb.hip",
            "stream_ops.hip", "vector_build.hip", "peaks.hip", "runs.hip", "region.hip", "display.hip", "trace.hip", "chain.hip",
-           "vsig_api.hip"]
-HEADERS = ["fft_engine.hpp", "os_common.hpp", "vsig_kernels.h", "npabs.hpp", "dtype.hpp", "dbmath.hpp", "xcorr_epilogue.hpp", "psd_traces_run.hpp"]
+           "api_core.hip", "api_transform.hip", "api_spectrum.hip", "api_filter.hip", "api_xcorr.hip", "api_detect.hip",
+           "api_vectors.hip"]
+HEADERS = ["fft_engine.hpp", "os_common.hpp", "vsig_kernels.h", "npabs.hpp", "dtype.hpp", "dbmath.hpp", "xcorr_epilogue.hpp", "psd_traces_run.hpp",
+           "vsig_ctx.hpp"]
+BUILD_ID_SOURCE = "api_core.hip"       # defines vsig_build_id(): the one unit compiled with the source hash
+API_HEADER = "vsig_ctx.hpp"            # included by the api_*.hip sources alone: an edit recompiles only those
 ARCH = os.environ.get("VSIG_ARCH", "gfx950")
 
 
@@ -56,21 +60,22 @@ OBJDIR = os.path.join(ROOT, "build", "objcache")
 
 
 def _compiler(defines=(), src=None):
-    """hipcc and its flags for one source (the build id goes into vsig_api.hip
-    alone, so an edit elsewhere recompiles only the edited unit and the API)."""
+    """hipcc and its flags for one source (the build id goes into api_core.hip
+    alone, so an edit elsewhere recompiles only the edited unit and that one)."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
              "-fno-slp-vectorize",   # SLP packs f32 pairs into v_pk_* + v_mov shuffles
              "-Wall", "-Wno-unused-function", *[f"-D{d}" for d in defines]]
-    if src == "vsig_api.hip":
+    if src == BUILD_ID_SOURCE:
         flags.append(f'-DVSIG_SRC_HASH="{source_hash()}"')
     return hipcc, flags
 
 
 def _unit_hash(src: str) -> str:
-    """The source and every shared header (any header edit recompiles all)."""
+    """The source and every header it can include (an edit of a kernel header
+    recompiles all, one of API_HEADER the C-ABI sources)."""
     h = hashlib.sha256()
-    for f in [src, *HEADERS]:
+    for f in [src, *(x for x in HEADERS if x != API_HEADER or src.startswith("api_"))]:
         h.update(open(os.path.join(CSRC, f), "rb").read())
     h.update(open(os.path.join(ROOT, "include", "vsig.h"), "rb").read())
     return h.hexdigest()

@@ -12,7 +12,7 @@
 // twiddles, inverse column pass) to natural order.  A consumer of the spectrum
 // itself gets it at its natural index from the row pass's store: |X|^2 for the
 // PSD of long frames (MODE 2), X through a BfOut for the DFT of a power of two
-// from 2^15 to 2^28 points (MODE 3: dft_any in vsig_api.hip runs those as this
+// from 2^15 to 2^28 points (MODE 3: dft_any, api_transform.hip, runs those as this
 // one transform of N points, not as a chirp-z).  Inverse transforms by conj:
 // IFFT(v) = conj(FFT(conj(v))).
 //
@@ -25,7 +25,7 @@
 // larger: column pass (load x c) -> row pass (FFT, * B, IFFT, same block) ->
 // inverse column pass (store c X).  The chirps are formed in double on the
 // device from n^2 mod 2N (exact integers).  A power of two from 256 points up
-// needs none of this: dft_any (vsig_api.hip) runs it as one transform, of its
+// needs none of this: dft_any (api_transform.hip) runs it as one transform, of its
 // own plan up to 16384 points (bf_small_kernel MODE 1, inverse by conj) and
 // four-step from 2^15 to 2^28, a half to a sixth of the max-norm error of the
 // chirp-z's three transforms (tests/test_gpu_accuracy.py,

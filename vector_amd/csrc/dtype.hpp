@@ -3,7 +3,7 @@
 // of their reductions, 16-byte packs, and the switch from a dtype code to the
 // element type.  Included by os_common.hpp (and through it by reduce.hip,
 // refine.hip, psd_traces.hip), peaks.hip, trace.hip, analysis.hip, display.hip
-// and vsig_api.hip.
+// and the C-ABI layer (vsig_ctx.hpp).
 #pragma once
 #include "npabs.hpp"
 #include "vsig_kernels.h"

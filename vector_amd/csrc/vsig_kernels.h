@@ -1,4 +1,4 @@
-// Internal interface between the C-ABI layer (vsig_api.hip) and the kernels.
+// Internal interface between the C-ABI layer (api_*.hip) and the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
