@@ -20,6 +20,9 @@
  *                     with find_correlation_peak               utils.py:1321-1334
  *   vsig_xcorr_bank_* K templates of one length against one stream in one pass
  *                     (the carrier-offset search; no reference counterpart)
+ *   vsig_match_*      every pair of K packets against each other in one pass: peak
+ *                     |correlation|, its lag and the energies (which bursts are
+ *                     one emitter's; no reference counterpart)
  *   vsig_peak_*       find_correlation_peak's |c| argmax / mean / std
  *                                                               utils.py:1321-1334
  *
@@ -146,7 +149,8 @@ int vsig_synchronize(vsig_ctx* ctx);
  * and of the spectrum traces (vsig_psd_traces_c64_dev):
  *   "psd_traces_batch" 0 (default): frames per stored batch by the 256 MB rule;
  *                     > 0: at most that many (nfft outside the in-LDS plans only).
- * and of the template bank (vsig_xcorr_bank_create): "xcorr_bank_m", see there. */
+ * and of the template bank (vsig_xcorr_bank_create): "xcorr_bank_m", see there;
+ * and of the all-pairs match (vsig_match_create): "match_grid", see there. */
 int vsig_set_option(vsig_ctx* ctx, const char* key, int value);
 int vsig_get_option(const vsig_ctx* ctx, const char* key, int* value);
 /* The hipStream_t the "refine_async" refine runs on (the context stream when
@@ -448,6 +452,58 @@ int vsig_xcorr_bank_exec_dev(vsig_xcorr_bank* bank, const void* s, int64_t n, in
  * walks blocks b, b + grid, ... */
 int vsig_xcorr_bank_plan(const vsig_xcorr_bank* bank, int64_t n, int32_t mode, int32_t* M,
                          int64_t* hop, int64_t* nblocks, int64_t* grid);
+
+/* ---- all-pairs burst similarity: which of K packets are the same packet sent again, and at
+ * what offset (match.hip).  Packets p_0 .. p_{K-1}, complex64, lengths 1 <= L_k <= 8192,
+ * packed back to back (p_k starts at the prefix sum of the lengths before it):
+ *   E_k     = sum_j |p_k[j]|^2
+ *   c_ab[l] = sum_j p_a[j + l] * conj(p_b[j]),  l in [-(L_b - 1), L_a - 1]
+ *             (np.correlate(p_a, p_b, 'full'), l = index - (L_b - 1))
+ *   peak[a,b] = max_l |c_ab[l]|,  lag[a,b] = the smallest l that attains it
+ * so lag[a,b] = l says that p_b's first sample lines up with p_a[l], and
+ * rho = peak / sqrt(E_a E_b) is in [0, 1].  For a < b the device computes the pair as
+ * written; (b,a) is its mirror: the same peak bits and lag[b,a] = -lag[a,b].  The diagonal
+ * is peak[a,a] = E_a rounded to float32, lag 0.  peak and lag are K x K row-major.
+ * The transform length N is the smallest of 1024 / 4096 / 8192 / 16384 with
+ * N >= 2 max(L_k) - 1.  One launch transforms every packet once into a K x N workspace the
+ * plan owns (and writes E and the diagonal), a second walks units (a, up to 8 consecutive
+ * b > a) on a persistent grid: the spectrum of a stays in registers, each b costs one
+ * spectrum product, one transform and the first maximum of the fp32 |c|^2 over the pair's
+ * valid lags only -- K + K(K-1)/2 transforms.  peak is v_sqrt of that maximum (1 ulp).
+ * Special values are decided from the energies (each a double sum, in a fixed order, of
+ * the fp32 |p|^2): if E_a or E_b is not finite (a NaN or Inf sample, or |p|^2 above
+ * FLT_MAX) the pair's peak is NaN and its lag 0, the diagonal included; if either is 0 the
+ * peak is 0 and the lag 0; every other pair's bytes are what they are without such a
+ * packet in the list.  The fp32 |c|^2 itself overflows where sqrt(E_a E_b) reaches
+ * 1.8e19 (sqrt(FLT_MAX)): constant-modulus packets of 8192 samples from an amplitude of
+ * about 4.7e7, of 512 samples from 1.9e8; the spectra (|P| <= L max|p|) and their product
+ * over N stay below that bound.  Past it a pair's peak is Inf or NaN and its lag
+ * arbitrary; underflow (sqrt(E_a E_b) below ~1e-19) loses the peak to 0 the same way.
+ * vsig_match_create validates everything before it touches the device, takes the lengths
+ *   from the HOST, builds the offsets and the unit table on the device and may
+ *   synchronise.  VSIG_E_INVALID: a NULL ctx / lens / out, K outside [1, 4096], a length
+ *   below 1; VSIG_E_UNSUPPORTED: a length above 8192; the message names the offending
+ *   packet.  The context option "match_grid" (0, the default: as many workgroups as the
+ *   device holds at once; > 0: at most that many) caps the launched grid of plans created
+ *   afterwards -- a measurement and test hook, so that one workgroup walks many units at a
+ *   small K; it changes no output byte.
+ * vsig_match_info: N, the pairs K(K-1)/2, the units, the launched grid, the workspace bytes.
+ * vsig_match_run takes DEVICE pointers: packed (complex64[sum of lens], 8-byte aligned),
+ *   peak (float[K*K]), lag (int32[K*K]), both 4-byte aligned, energy (double[K], 8-byte
+ *   aligned); a NULL or misaligned pointer is VSIG_E_INVALID before any work is enqueued.
+ *   It enqueues on the context stream, allocates nothing, never synchronises and can be
+ *   captured into a graph.  packed is read at [0, sum of lens) only; peak, lag and energy
+ *   are written exactly, each element once.  No atomics and a fixed walk order: the same
+ *   input gives the same bytes on every run and from every plan, and a pair's record does
+ *   not depend on the other packets of the list or on K, as long as a < b is kept and the
+ *   list's longest packet asks for the same N.
+ * vsig_match_free waits for the context stream, then frees the plan. */
+typedef struct vsig_match vsig_match;
+int vsig_match_create(vsig_ctx* ctx, const int64_t* lens /*host, K*/, int32_t K, vsig_match** out);
+void vsig_match_free(vsig_match* plan);
+int vsig_match_info(const vsig_match* plan, int32_t* N, int64_t* pairs, int64_t* units, int64_t* grid,
+                    int64_t* workspace_bytes);
+int vsig_match_run(vsig_match* plan, const void* packed, float* peak, int32_t* lag, double* energy);
 
 /* ---- general correlation, np.correlate(a, v, mode) semantics for any length
  * order (cross_correlate_signals, utils.py:1279-1285): output length full

@@ -188,6 +188,11 @@ SIGNATURES = {
     "vsig_xcorr_bank_exec_dev": (C.c_int, [P, P, I64, I32, P, P]),
     "vsig_xcorr_bank_plan": (C.c_int, [P, I64, I32, C.POINTER(I32), C.POINTER(I64), C.POINTER(I64),
                                        C.POINTER(I64)]),
+    "vsig_match_create": (C.c_int, [P, C.POINTER(I64), I32, C.POINTER(P)]),
+    "vsig_match_free": (None, [P]),
+    "vsig_match_info": (C.c_int, [P, C.POINTER(I32), C.POINTER(I64), C.POINTER(I64), C.POINTER(I64),
+                                  C.POINTER(I64)]),
+    "vsig_match_run": (C.c_int, [P, P, P, P, P]),
     "vsig_correlate_dev": (C.c_int, [P, I32, P, I64, P, I64, I32, I32, P, P]),
     "vsig_correlate": (C.c_int, [P, I32, P, I64, P, I64, I32, I32, P, P]),
     "vsig_correlate_c64_dev": (C.c_int, [P, P, I64, P, I64, I32, P, P]),

@@ -230,6 +230,9 @@ int vsig_set_option(vsig_ctx* c, const char* key, int value) {
     if (value != 0 && value != 4096 && value != 8192 && value != 16384)
       return fail(c, VSIG_E_INVALID, "xcorr_bank_m must be 0, 4096, 8192 or 16384");
     c->xcorr_bank_m = value;
+  } else if (k == "match_grid") {
+    if (value < 0) return fail(c, VSIG_E_INVALID, "match_grid must be >= 0");
+    c->match_grid = value;
   } else if (k == "refine_async") {
     vsig_ctx::RefineAsync& ra = c->ra;
     if (value && !ra.stream) {
@@ -261,6 +264,7 @@ int vsig_get_option(const vsig_ctx* c, const char* key, int* value) {
   else if (k == "refine_async") *value = c->refine_async;
   else if (k == "psd_traces_batch") *value = (int)c->psd_traces_batch;
   else if (k == "xcorr_bank_m") *value = c->xcorr_bank_m;
+  else if (k == "match_grid") *value = c->match_grid;
   else return VSIG_E_INVALID;
   return VSIG_OK;
 }

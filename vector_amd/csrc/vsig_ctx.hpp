@@ -92,6 +92,7 @@ struct vsig_ctx {
   DevBuf ptscratch;                      // psd_traces.hip record rows (+ the fold route's frame batch)
   long long psd_traces_batch = 0;        // fold route: frames per batch at most (0: the 256 MB rule)
   int xcorr_bank_m = 0;                  // template bank block size (0: by template length)
+  int match_grid = 0;                    // all-pairs match: cap on the launched grid (0: the resident blocks)
   PeakPartial* parts() const { return partials.as<PeakPartial>(); }
   // the first-level buffer of a two-level finalize, right after the partials,
   // then the fused finalize's block counters (zero between launches)
@@ -184,6 +185,18 @@ struct vsig_isolate {
   explicit vsig_isolate(vsig_ctx* c) : ctx(c) {}
   // the stream may still use the tables: wait, then the members free them
   ~vsig_isolate() { (void)hipStreamSynchronize(ctx->stream); }
+};
+
+// The tables and the K x N spectra of one packet list (vsig_match_create).
+struct vsig_match {
+  vsig_ctx* ctx;
+  int K = 0, N = 0, tile = 0;
+  long long total = 0, pairs = 0, nunits = 0, grid = 0;
+  const float2* tw = nullptr;      // the context's cached table
+  DevBuf offsets, units, W;
+  explicit vsig_match(vsig_ctx* c) : ctx(c) {}
+  // the stream may still use the tables: wait, then the members free them
+  ~vsig_match() { (void)hipStreamSynchronize(ctx->stream); }
 };
 
 // A bank of K templates of one length L <= kBankMaxL: the K spectra of M

@@ -240,6 +240,17 @@ hipError_t launch_xcorr_bank(int M, const float2* s, long long n, const float2* 
 // out[k] = the record (max |c|, first index, sums) of group k of nparts partials
 hipError_t launch_bank_finalize(const PeakPartial* parts, int K, long long nparts, PeakPartial* out,
                                 hipStream_t st);
+// match.hip: every pair of K packed packets in one pass (vsig_match_run; see
+// the file's header), N in {1024, 4096, 8192, 16384}.  A unit is packet a
+// against b0 .. b0 + nb - 1, all > a and < K.
+struct MatchUnit { int a, b0, nb, pad; };
+// the twiddle table's key for N, and the pair kernel's resident blocks (CUs x blocks per CU)
+hipError_t match_geom(int N, int* table_key, long long* resident);
+// offsets: K + 1 prefix sums of the lengths; W: K x N workspace; peak / lag: K x K;
+// energy: K.  The spectra launch (K blocks), then the pair launch (grid blocks over nunits).
+hipError_t launch_match(int N, const float2* packed, const long long* offsets, int K, float2* W,
+                        double* energy, const MatchUnit* units, long long nunits, long long grid,
+                        float* peak, int* lag, const float2* tw, hipStream_t st);
 #ifdef VSIG_TUNING
 // Tuning micro-benchmarks: iters FFTs per frame, frames blocks (key: plan key).
 hipError_t launch_fft_bench(int key, float2* io, int frames, int iters, const float2* tw, int twl,
