@@ -23,6 +23,9 @@
  *   vsig_match_*      every pair of K packets against each other in one pass: peak
  *                     |correlation|, its lag and the energies (which bursts are
  *                     one emitter's; no reference counterpart)
+ *   vsig_combine_*    the bursts of one emitter averaged coherently into one packet, with
+ *                     a gain, a frequency and an SNR per instance (the clean packet the
+ *                     reference's users cut by hand; no reference counterpart)
  *   vsig_peak_*       find_correlation_peak's |c| argmax / mean / std
  *                                                               utils.py:1321-1334
  *
@@ -504,6 +507,88 @@ void vsig_match_free(vsig_match* plan);
 int vsig_match_info(const vsig_match* plan, int32_t* N, int64_t* pairs, int64_t* units, int64_t* grid,
                     int64_t* workspace_bytes);
 int vsig_match_run(vsig_match* plan, const void* packed, float* peak, int32_t* lag, double* energy);
+
+/* ---- coherent averaging of an emitter's repeats: the bursts vsig_match_run found to be one
+ * packet sent again, summed into one packet of up to M times the SNR, with a per-instance
+ * SNR from the same sums (no reference counterpart).  K packets p_k (complex64, lengths
+ * L_k >= 1) packed back to back; G groups; group[k] in [-1, G) (-1: not combined); lag[k] =
+ * d_k, the match's lag[k, rep]: the representative's sample j lines up with p_k[j + d_k];
+ * rep[g] a member of g with d = 0.  y_g, group g's output, has the representative's length
+ * L_g and lives in its sample frame; the outputs are packed back to back in group order
+ * (vsig_combine_offsets).  All ranges half open.
+ * Estimate of member k against a reference v of length L_g and a prior frequency f0_k
+ * (cycles per sample): the overlap is lo = max(0, -d_k), hi = min(L_g, L_k - d_k), n = hi -
+ * lo; h = n / 2 (integer), m = lo + (n - 1) / 2;
+ *   z[j] = p_k[j + d_k] * exp(-2j*pi*f0_k*(j - m)) * conj(v[j]),  j in [lo, hi)
+ *   A1 = sum z over the first h samples, A2 over the rest; Ep1, Ep2 the same sums of
+ *   |p_k[j + d_k]|^2, Ev1, Ev2 of |v[j]|^2;  Ep = Ep1 + Ep2, Ev = Ev1 + Ev2
+ *   phi  = arg(A2 conj(A1))  (0 when A1 == 0 or A2 == 0)
+ *   freq = f0_k + phi / (pi n)               the halves' centres are n / 2 apart
+ *   B    = A1 exp(+j phi/2) + A2 exp(-j phi/2)
+ *   a    = B / Ev                            the complex gain at the overlap's centre
+ *   rho  = |B| / sqrt(Ep Ev)
+ *   res  = Ep - (|A1|^2 / Ev1 + |A2|^2 / Ev2)     a term whose Ev is 0 is dropped
+ * used = n > 0, every sum finite, Ev > 0 and rho >= min_rho (an all-zero member has rho
+ * 0/0 and is not used); otherwise a = 0, freq = f0_k, rho = 0 (NaN if a sum is not
+ * finite).  n, m, Ep, Ev and res are written as computed either way; a packet in group -1
+ * has used = 0, n = 0, freq = f0_k and every other field 0.  With ref == NULL the reference
+ * is the representative inside packed, and the representative's own record is a = 1, freq =
+ * 0, rho = 1, res = 0, used = 1 by definition (Ep = Ev = its energy).
+ * Sum (maximum-ratio combining), j in [0, L_g):
+ *   y_g[j] = sum_k conj(a_k) exp(-2j*pi*freq_k*(j - m_k)) p_k[j + d_k] / sum_k |a_k|^2
+ * both sums over the used members of g that cover j (0 <= j + d_k < L_k), in ascending k;
+ * 0 where none does.  freq == 0 and a == 1 multiply nothing and a denominator of 1 divides
+ * nothing, so a group of one member gives back its packet's bytes.
+ * Arithmetic: the products of the estimate are fp32 (uncontracted: p against itself has an
+ * imaginary part of exactly 0), widened to double and added in double in a fixed order in
+ * chunks of S = 2048 samples of the overlap (vsig_combine_info's chunk), one fixed-slot
+ * partial a chunk in the plan's workspace, then per member in chunk order; the rotations
+ * are fp32 on a phase formed in double; the sum accumulates in fp32.  No atomics: a record
+ * is a function of its member, its reference, f0 and S, an output sample of its group's
+ * members, and neither depends on K, on the other groups or on the grid.
+ * vsig_combine_create validates everything before it touches the device, takes all four
+ *   lists from the HOST, builds the member, group and item tables on the device and may
+ *   synchronise.  VSIG_E_INVALID, the message naming the offending packet or group: a NULL
+ *   pointer, K outside [1, 4096], G outside [1, K], a length below 1, a group id outside
+ *   [-1, G), a representative that is not a member of its group or whose lag is not 0;
+ *   VSIG_E_UNSUPPORTED: 2^31 packed samples or more.  A lag beyond every length is valid
+ *   (no overlap).
+ * vsig_combine_info: the packed output's length, S, the estimate items (one per member and
+ *   chunk of its overlap), the sum items (one per group and chunk of 512 samples of its
+ *   output) and the workspace bytes (64 an estimate item).
+ * vsig_combine_offsets: the G + 1 prefix sums of the outputs into a HOST array.
+ * vsig_combine_estimate and vsig_combine_sum take DEVICE pointers, all 8-byte aligned:
+ *   packed (complex64[sum of lens]), ref (NULL, or complex64[out_total] in the output
+ *   layout), f0 (NULL = 0, or double[K]), records ([K]), y (complex64[out_total]); a NULL
+ *   packed / records / y, a misaligned pointer or a NaN min_rho is VSIG_E_INVALID before
+ *   any work is enqueued.  They enqueue on the context stream, allocate nothing, never
+ *   synchronise and can be captured into a graph.  Inputs are read inside their extents
+ *   only; estimate writes every record whole (80 bytes, pad 0), sum every element of y
+ *   once.  Every address is formed from the plan's tables, never from a record's fields.
+ *   Two estimates of one plan share its workspace: they run in stream order.
+ * vsig_combine_free waits for the context stream, then frees the plan. */
+typedef struct vsig_combine_member_t {
+  double a_re, a_im; /* complex gain against the reference at the overlap's centre */
+  double freq;       /* cycles per sample */
+  double m;          /* the overlap's centre lo + (n - 1) / 2, in the group's frame */
+  double rho;        /* normalised correlation with the reference, in [0, 1] */
+  double Ep, Ev;     /* the member's and the reference's energy over the overlap */
+  double res;        /* Ep minus what the two-half fit explains */
+  int64_t n;         /* overlap, samples */
+  int32_t used;      /* 1: part of the sum */
+  int32_t pad;
+} vsig_combine_member_t;
+typedef struct vsig_combine vsig_combine;
+int vsig_combine_create(vsig_ctx* ctx, const int64_t* lens /*host, K*/, const int32_t* group /*host, K, -1 = none*/,
+                        const int64_t* lag /*host, K*/, int32_t K, const int32_t* rep /*host, G*/, int32_t G,
+                        vsig_combine** out);
+void vsig_combine_free(vsig_combine* plan);
+int vsig_combine_info(const vsig_combine* plan, int64_t* out_total, int32_t* chunk /*S*/, int64_t* est_items,
+                      int64_t* sum_items, int64_t* workspace_bytes);
+int vsig_combine_offsets(const vsig_combine* plan, int64_t* offsets /*host, G + 1*/);
+int vsig_combine_estimate(vsig_combine* plan, const void* packed, const void* ref, const double* f0,
+                          double min_rho, vsig_combine_member_t* records);
+int vsig_combine_sum(vsig_combine* plan, const void* packed, const vsig_combine_member_t* records, void* y);
 
 /* ---- general correlation, np.correlate(a, v, mode) semantics for any length
  * order (cross_correlate_signals, utils.py:1279-1285): output length full

@@ -30,7 +30,8 @@ from .display import (SpectrogramImage, colormap_table, image_extent, plot_spect
 from .traces import Trace, averaged_spectrum_trace, capture_spectrum, signal_envelope, trace_bin  # noqa: F401
 from .packets import (IsolatedPackets, PacketMeasurements, SegmentSpectra, design_lowpass,  # noqa: F401
                       isolate_packets, measure_packets, segment_spectra)
-from .match import (GroupTiming, PacketGroups, PacketMatches, Similarity, cluster_carriers,  # noqa: F401
-                    group_packets, group_timing, match_packets, packet_similarity)
+from .match import (CombinedPackets, CombineMembers, GroupTiming, PacketGroups, PacketMatches,  # noqa: F401
+                    Similarity, cluster_carriers, combine_packets, group_packets, group_timing, match_packets,
+                    packet_similarity)
 
 __version__ = "0.1.0"

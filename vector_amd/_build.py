@@ -15,11 +15,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvsig.so")
-SOURCES = ["psd.hip", "psd_traces.hip", "psd_segments.hip", "fir.hip", "isolate.hip", "xcorr.hip", "xcorr_bank.hip", "match.hip", "reduce.hip", "refine.hip", "bigfft.hip", "analysis.hip", "pfb.hip",
+SOURCES = ["psd.hip", "psd_traces.hip", "psd_segments.hip", "fir.hip", "isolate.hip", "xcorr.hip", "xcorr_bank.hip", "match.hip", "combine.hip", "reduce.hip", "refine.hip", "bigfft.hip", "analysis.hip", "pfb.hip",
            "stream_ops.hip", "vector_build.hip", "peaks.hip", "runs.hip", "region.hip", "display.hip", "trace.hip", "chain.hip",
            "api_core.hip", "api_transform.hip", "api_spectrum.hip", "api_filter.hip", "api_xcorr.hip", "api_detect.hip",
-           "api_vectors.hip", "api_match.hip"]
-HEADERS = ["fft_engine.hpp", "os_common.hpp", "vsig_kernels.h", "npabs.hpp", "dtype.hpp", "dbmath.hpp", "xcorr_epilogue.hpp", "psd_traces_run.hpp",
+           "api_vectors.hip", "api_match.hip", "api_combine.hip"]
+HEADERS = ["fft_engine.hpp", "os_common.hpp", "vsig_kernels.h", "combine_plan.hpp", "npabs.hpp", "dtype.hpp", "dbmath.hpp", "xcorr_epilogue.hpp", "psd_traces_run.hpp",
            "vsig_ctx.hpp"]
 BUILD_ID_SOURCE = "api_core.hip"       # defines vsig_build_id(): the one unit compiled with the source hash
 API_HEADER = "vsig_ctx.hpp"            # included by the api_*.hip sources alone: an edit recompiles only those

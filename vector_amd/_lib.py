@@ -134,6 +134,19 @@ class IsolateSeg(C.Structure):
     _fields_ = [("start", I64), ("len", I64), ("freq", C.c_double), ("filter", I32), ("pad", I32)]
 
 
+class CombineMember(C.Structure):
+    """vsig_combine_member_t (include/vsig.h)."""
+    _fields_ = [("a_re", C.c_double), ("a_im", C.c_double), ("freq", C.c_double), ("m", C.c_double),
+                ("rho", C.c_double), ("Ep", C.c_double), ("Ev", C.c_double), ("res", C.c_double),
+                ("n", I64), ("used", I32), ("pad", I32)]
+
+
+# the same record as a numpy dtype: a device buffer of K records read back in one copy
+COMBINE_MEMBER = np.dtype([("a_re", "<f8"), ("a_im", "<f8"), ("freq", "<f8"), ("m", "<f8"), ("rho", "<f8"),
+                           ("Ep", "<f8"), ("Ev", "<f8"), ("res", "<f8"), ("n", "<i8"), ("used", "<i4"),
+                           ("pad", "<i4")])
+
+
 # name -> (restype, argtypes); every symbol include/vsig.h declares.
 SIGNATURES = {
     "vsig_version": (C.c_int, []),
@@ -193,6 +206,14 @@ SIGNATURES = {
     "vsig_match_info": (C.c_int, [P, C.POINTER(I32), C.POINTER(I64), C.POINTER(I64), C.POINTER(I64),
                                   C.POINTER(I64)]),
     "vsig_match_run": (C.c_int, [P, P, P, P, P]),
+    "vsig_combine_create": (C.c_int, [P, C.POINTER(I64), C.POINTER(I32), C.POINTER(I64), I32, C.POINTER(I32), I32,
+                                      C.POINTER(P)]),
+    "vsig_combine_free": (None, [P]),
+    "vsig_combine_info": (C.c_int, [P, C.POINTER(I64), C.POINTER(I32), C.POINTER(I64), C.POINTER(I64),
+                                    C.POINTER(I64)]),
+    "vsig_combine_offsets": (C.c_int, [P, C.POINTER(I64)]),
+    "vsig_combine_estimate": (C.c_int, [P, P, P, P, C.c_double, P]),
+    "vsig_combine_sum": (C.c_int, [P, P, P, P]),
     "vsig_correlate_dev": (C.c_int, [P, I32, P, I64, P, I64, I32, I32, P, P]),
     "vsig_correlate": (C.c_int, [P, I32, P, I64, P, I64, I32, I32, P, P]),
     "vsig_correlate_c64_dev": (C.c_int, [P, P, I64, P, I64, I32, P, P]),

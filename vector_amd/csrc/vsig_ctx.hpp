@@ -199,6 +199,18 @@ struct vsig_match {
   ~vsig_match() { (void)hipStreamSynchronize(ctx->stream); }
 };
 
+// The tables and the estimate partials of one grouped packet list (vsig_combine_create).
+struct vsig_combine {
+  vsig_ctx* ctx;
+  int K = 0, G = 0;
+  long long total = 0, out_total = 0, est_items = 0, sum_items = 0;
+  std::vector<long long> offsets;  // G + 1 prefix sums of the packed output
+  DevBuf mem, grp, csr, est, sum, parts;
+  explicit vsig_combine(vsig_ctx* c) : ctx(c) {}
+  // the stream may still use the tables: wait, then the members free them
+  ~vsig_combine() { (void)hipStreamSynchronize(ctx->stream); }
+};
+
 // A bank of K templates of one length L <= kBankMaxL: the K spectra of M
 // points in one table (row k at Ps + k M).
 struct vsig_xcorr_bank {

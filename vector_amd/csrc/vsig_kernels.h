@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "combine_plan.hpp"
+
 namespace vsig {
 
 // XCD-aware block order.  The dispatcher hands block b to XCD b % 8 and each
@@ -251,6 +253,17 @@ hipError_t match_geom(int N, int* table_key, long long* resident);
 hipError_t launch_match(int N, const float2* packed, const long long* offsets, int K, float2* W,
                         double* energy, const MatchUnit* units, long long nunits, long long grid,
                         float* peak, int* lag, const float2* tw, hipStream_t st);
+// combine.hip: coherent averaging of grouped packets (vsig_combine_*; see the
+// file's header and combine_plan.hpp for the tables).  estimate: nitems items
+// into their partials, then every packet's record (ref null: against the
+// representatives in packed, whose own records are a = 1 by definition; f0
+// null: 0).  sum: nitems (group, chunk) items write y exactly.
+hipError_t launch_combine_estimate(const float2* packed, const float2* ref, const double* f0,
+                                   const CombineMember* mem, int K, const CombineItem* items, long long nitems,
+                                   CombinePartial* parts, double min_rho, CombineRecord* rec, hipStream_t st);
+hipError_t launch_combine_sum(const float2* packed, const CombineMember* mem, const CombineGroup* grp,
+                              const int* csr, const CombineItem* items, long long nitems,
+                              const CombineRecord* rec, float2* y, hipStream_t st);
 #ifdef VSIG_TUNING
 // Tuning micro-benchmarks: iters FFTs per frame, frames blocks (key: plan key).
 hipError_t launch_fft_bench(int key, float2* io, int frames, int iters, const float2* tw, int twl,

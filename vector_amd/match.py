@@ -7,6 +7,9 @@ period: the analysis path's last step, capture -> plan -> build_vector.
   group_packets      emitters: the connected components of rho >= threshold
   group_timing       each emitter's first arrival, period, count and jitter
   cluster_carriers   bursts' measured centres merged into carriers
+  combine_packets    every emitter's bursts averaged coherently into one clean
+                     packet, with a gain, a frequency and an SNR per instance
+                     (vsig_combine_estimate / vsig_combine_sum)
   match_packets      the whole path from a capture and its burst list to the
                      ``configs`` that vector_plan / build_vector accept
 
@@ -24,13 +27,21 @@ from . import _lib
 from .dsp import _is_dev, _ptr
 from .packets import _check_ntaps, _check_segments, _per_burst, _signal_length, isolate_packets, measure_packets
 
-__all__ = ["Similarity", "PacketGroups", "GroupTiming", "PacketMatches", "packet_similarity", "group_packets",
-           "group_timing", "cluster_carriers", "match_packets"]
+__all__ = ["Similarity", "PacketGroups", "GroupTiming", "PacketMatches", "CombinedPackets", "CombineMembers",
+           "packet_similarity", "group_packets", "group_timing", "cluster_carriers", "combine_packets", "match_packets"]
 
 Similarity = namedtuple("Similarity", "rho lag energy")
 PacketGroups = namedtuple("PacketGroups", "labels groups representative")
-PacketMatches = namedtuple("PacketMatches",
-                           "similarity groups timing carriers carrier_of measurements isolated configs")
+CombinedPackets = namedtuple("CombinedPackets", "packets gain members")
+CombineMembers = namedtuple("CombineMembers", "a freq rho snr overlap used")
+
+
+class PacketMatches(namedtuple("PacketMatches",
+                               "similarity groups timing carriers carrier_of measurements isolated configs")):
+    """match_packets' result; ``combined`` is the CombinedPackets of
+    match_packets(..., combine=True), else None."""
+    combined = None
+
 
 MATCH_MAX_K = 4096
 MATCH_MAX_L = 8192
@@ -58,8 +69,9 @@ def match_size(lmax):
     return 16384
 
 
-def _check_packets(packets, max_samples):
-    """(list of 1-D complex64 prefixes, lengths, all-device flag), with no device."""
+def _check_packets(packets, max_samples, cap=MATCH_MAX_L, who="packet_similarity"):
+    """(list of 1-D complex64 prefixes, lengths, all-device flag), with no
+    device.  cap: the longest packet taken (None: any length)."""
     if hasattr(packets, "packets") and hasattr(packets, "cutoff"):      # IsolatedPackets
         packets = packets.packets
     if isinstance(packets, (np.ndarray, torch.Tensor)):
@@ -73,7 +85,7 @@ def _check_packets(packets, max_samples):
             raise ValueError(f"max_samples must be at most {MATCH_MAX_L}")
     K = len(packets)
     if K < 1 or K > MATCH_MAX_K:
-        raise ValueError(f"packet_similarity takes 1 to {MATCH_MAX_K} packets ({K} given)")
+        raise ValueError(f"{who} takes 1 to {MATCH_MAX_K} packets ({K} given)")
     dev = [_is_dev(p) for p in packets]
     if any(dev) and not all(dev):
         raise ValueError("packets must be all numpy arrays or all CUDA tensors")
@@ -91,7 +103,7 @@ def _check_packets(packets, max_samples):
             raise ValueError(f"packet {k} is empty")
         if max_samples is not None:
             p = p[:max_samples]
-        if p.shape[0] > MATCH_MAX_L:
+        if cap is not None and p.shape[0] > cap:
             raise ValueError(f"packet {k} has {p.shape[0]} samples: packet_similarity compares at most "
                              f"{MATCH_MAX_L}; pass max_samples to compare prefixes")
         out.append(p)
@@ -332,6 +344,158 @@ def cluster_carriers(centers, bandwidths, freq_tol=None):
     return carrier_of, np.array(carriers, np.float64)
 
 
+COMBINE_MAX_TOTAL = 1 << 31
+
+
+def _check_min_rho(min_rho):
+    min_rho = float(min_rho)
+    if np.isnan(min_rho) or min_rho > 1:
+        raise ValueError("min_rho must be a number no larger than 1")
+    return min_rho
+
+
+def _check_groups(groups, lag, K):
+    """(group int32 K, lag-to-representative int64 K, representative int32 G)
+    of a PacketGroups or a list of member index arrays, with no device."""
+    if hasattr(groups, "representative"):
+        members, reps = list(groups.groups), [int(r) for r in np.asarray(groups.representative)]
+    else:
+        if isinstance(groups, (np.ndarray, torch.Tensor)):
+            raise ValueError("groups must be a PacketGroups or a list of member index arrays")
+        members = list(groups)
+        reps = None
+    members = [np.asarray(_host(m, np.int64)).reshape(-1) for m in members]
+    G = len(members)
+    if G < 1:
+        raise ValueError("combine_packets needs at least one group")
+    if reps is None:
+        if any(m.size < 1 for m in members):
+            raise ValueError("a group is empty")
+        reps = [int(m[0]) for m in members]
+    lag = _host(lag, np.int64)
+    if lag.shape != (K, K):
+        raise ValueError(f"lag must be the K x K matrix of packet_similarity ({K} x {K})")
+    group = np.full(K, -1, np.int32)
+    for g, m in enumerate(members):
+        if m.size < 1 or m.min() < 0 or m.max() >= K:
+            raise ValueError(f"group {g} is empty or names a packet outside [0, {K})")
+        if np.unique(m).size != m.size or np.any(group[m] >= 0):
+            raise ValueError(f"group {g} names a packet twice or one that another group holds")
+        group[m] = g
+        if reps[g] not in m:
+            raise ValueError(f"group {g}'s representative {reps[g]} is not one of its members")
+        if lag[reps[g], reps[g]] != 0:
+            raise ValueError(f"group {g}'s representative {reps[g]} has a lag to itself")
+    reps = np.asarray(reps, np.int32)
+    ok = group >= 0
+    d = np.zeros(K, np.int64)
+    d[ok] = lag[np.flatnonzero(ok), reps[group[ok]]]
+    return group, d, reps
+
+
+def _records_host(rec):
+    return rec.cpu().numpy().view(_lib.COMBINE_MEMBER).reshape(-1)
+
+
+def combine_packets(packets, groups, lag, *, min_rho=0.0, refine=False):
+    """Each group's bursts averaged coherently into one packet ->
+    CombinedPackets(packets, gain, members).
+
+    packets: the K bursts (a list of 1-D complex64 arrays or CUDA tensors, or
+    an IsolatedPackets: the full isolated bursts, of any length -- lags found
+    on prefixes still hold); groups: group_packets' PacketGroups, or a list of
+    member index arrays whose first entry is the representative (a packet no
+    group names is left out); lag: packet_similarity's K x K matrix.
+
+    Group g's packet lives in its representative's sample frame and has its
+    length.  Every other member is first measured against the representative
+    over their overlap -- a complex gain a_k, a residual frequency freq_k
+    (cycles per sample, from the phase between the two halves of the overlap)
+    and the normalised correlation rho_k -- then
+
+      y_g[j] = sum_k conj(a_k) exp(-2j pi freq_k (j - m_k)) p_k[j + d_k] / sum_k |a_k|^2
+
+    over the members that cover j (maximum-ratio combining; m_k the overlap's
+    centre, d_k = lag[k, representative]).  A member with rho_k < min_rho, with
+    a NaN or Inf sample, all zero or without overlap is not used (it is
+    skipped, not added as zero); a group of one returns its packet's bytes.
+    A second measurement against y_g, with freq_k as the prior, gives the
+    per-instance SNR; refine=True sums once more with that second
+    measurement's gains and frequencies.
+
+      packets  G views of one packed complex64 buffer
+      gain     float64 (G,): sum |a_k|^2 over the used members -- the predicted
+               SNR of y_g over the representative alone
+      members  CombineMembers(a complex128, freq, rho, snr, overlap, used), each
+               (K,): the first measurement (the representative's own: a = 1,
+               freq = 0, rho = 1), the overlap in samples, and snr_k = (Ep -
+               res) / res (1 - |a_k|^2 / gain_g) from the second: signal over
+               residual power against y_g, less the member's own noise inside
+               y_g (inf where nothing is left over; NaN for a packet in no
+               group, without overlap or with a non-finite sample)
+
+    Three launches a pass on tables built once (vsig_combine_estimate, _sum,
+    _estimate), whatever K and G are.  numpy in -> numpy out; CUDA tensors in
+    -> tensors on their device, packed views used in place.  Every argument
+    error is raised before the device is touched."""
+    pk, lens, dev_in = _check_packets(packets, None, cap=None, who="combine_packets")
+    K = int(lens.size)
+    if int(lens.sum()) >= COMBINE_MAX_TOTAL:
+        raise NotImplementedError("combine_packets: the packets hold 2^31 samples or more")
+    group, d, reps = _check_groups(groups, lag, K)
+    min_rho = _check_min_rho(min_rho)
+    refine = bool(refine)
+    G = int(reps.size)
+    ctx = _lib.get_context()
+    if dev_in:
+        packed = _packed_in_place(pk, lens)
+        if packed is None:
+            packed = torch.cat([p.to(f"cuda:{ctx.device}") for p in pk])
+    else:
+        packed = torch.from_numpy(np.ascontiguousarray(np.concatenate(pk))).to(f"cuda:{ctx.device}")
+    dev = packed.device
+    plan = _lib.P()
+    I64P, I32P = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+    ctx.check(ctx.lib.vsig_combine_create(ctx.h, lens.ctypes.data_as(I64P), group.ctypes.data_as(I32P),
+                                          d.ctypes.data_as(I64P), K, reps.ctypes.data_as(I32P), G, C.byref(plan)),
+              "combine_packets")
+    try:
+        offsets = np.zeros(G + 1, np.int64)
+        ctx.check(ctx.lib.vsig_combine_offsets(plan, offsets.ctypes.data_as(I64P)), "combine_packets")
+        nrec = _lib.COMBINE_MEMBER.itemsize
+        rec1 = torch.empty(K * nrec, dtype=torch.uint8, device=dev)
+        rec2 = torch.empty(K * nrec, dtype=torch.uint8, device=dev)
+        y = torch.empty(int(offsets[G]), dtype=torch.complex64, device=dev)
+        ctx.check(ctx.lib.vsig_combine_estimate(plan, _ptr(packed), None, None, min_rho, _ptr(rec1)), "combine_packets")
+        ctx.check(ctx.lib.vsig_combine_sum(plan, _ptr(packed), _ptr(rec1), _ptr(y)), "combine_packets")
+        f0 = rec1.view(torch.float64).view(K, nrec // 8)[:, 2].contiguous()
+        ctx.check(ctx.lib.vsig_combine_estimate(plan, _ptr(packed), _ptr(y), _ptr(f0), min_rho, _ptr(rec2)),
+                  "combine_packets")
+        if refine:
+            ctx.check(ctx.lib.vsig_combine_sum(plan, _ptr(packed), _ptr(rec2), _ptr(y)), "combine_packets")
+    finally:
+        ctx.lib.vsig_combine_free(plan)            # waits for the launches: the plan owns their tables
+    first, second = _records_host(rec1), _records_host(rec2)
+    used = first["used"] != 0
+    a = first["a_re"] + 1j * first["a_im"]
+    power = np.where(used, np.abs(a) ** 2, 0.0)
+    gain = np.array([power[group == g].sum() for g in range(G)])
+    snr = np.full(K, np.nan)
+    with np.errstate(all="ignore"):
+        ok = (group >= 0) & (second["n"] > 0) & np.isfinite(second["Ep"]) & np.isfinite(second["res"])
+        share = np.where(used & ok, power / np.where(ok, gain[np.maximum(group, 0)], 1.0), 0.0)
+        share = np.where(np.isfinite(share), share, 0.0)
+        res = second["res"]
+        snr[ok] = np.where(res[ok] <= 0, np.inf, (second["Ep"][ok] - res[ok]) / res[ok] * (1 - share[ok]))
+    members = CombineMembers(a, first["freq"].copy(), first["rho"].copy(), snr, first["n"].copy(), used)
+    if dev_in:
+        out = [y[int(offsets[g]):int(offsets[g + 1])] for g in range(G)]
+        return CombinedPackets(out, torch.from_numpy(gain).to(dev),
+                               CombineMembers(*(torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in members)))
+    yh = y.cpu().numpy()
+    return CombinedPackets([yh[int(offsets[g]):int(offsets[g + 1])] for g in range(G)], gain, members)
+
+
 def _seconds_for(samples, sample_rate, trunc):
     """A time t with int(t * sample_rate) (trunc) or int(round(t * sample_rate))
     equal to ``samples`` where that is a whole number within 1e-6; else
@@ -347,7 +511,7 @@ def _seconds_for(samples, sample_rate, trunc):
 
 
 def match_packets(signal, packets, sample_rate, center_freq=0.0, *, threshold=0.7, freq_tol=None, ntaps=255,
-                  max_samples=4096, pre_samples=0, post_samples=0, measurements=None):
+                  max_samples=4096, pre_samples=0, post_samples=0, measurements=None, combine=False, min_rho=0.0):
     """From a capture and its burst list to emitters and their timing ->
     PacketMatches(similarity, groups, timing, carriers, carrier_of,
     measurements, isolated, configs).
@@ -368,6 +532,9 @@ def match_packets(signal, packets, sample_rate, center_freq=0.0, *, threshold=0.
     vector_plan's int() / round() give back the recovered whole samples),
     ``freq_shift`` = carrier - center_freq.  A group of one burst has the
     capture's duration as its period (one instance).
+    combine=True: combine_packets(isolated, groups, lag, min_rho=min_rho) --
+    every group's bursts averaged coherently -- is returned as ``.combined``
+    and its packets are the configs' ``signal`` in place of one noisy instance.
     packets: detect_packets' Packets or a (starts, ends) pair, inclusive ends;
     complex64 signals only; numpy in -> numpy out.  Every argument error is
     raised before the device is touched."""
@@ -400,6 +567,9 @@ def match_packets(signal, packets, sample_rate, center_freq=0.0, *, threshold=0.
     pre_samples, post_samples = int(pre_samples), int(post_samples)
     if pre_samples < 0 or post_samples < 0:
         raise ValueError("pre_samples and post_samples must be >= 0")
+    if not isinstance(combine, (bool, np.bool_)):
+        raise ValueError("combine must be True or False")
+    min_rho = _check_min_rho(min_rho)
     if measurements is not None:
         for name in ("center_freq", "bandwidth"):
             _per_burst(f"measurements.{name}", getattr(measurements, name), K)
@@ -426,4 +596,9 @@ def match_packets(signal, packets, sample_rate, center_freq=0.0, *, threshold=0.
                         "start_time": _seconds_for(max(0.0, timing.start[g]), sample_rate, False),
                         "period": _seconds_for(period, sample_rate, True),
                         "freq_shift": 0.0 if np.isnan(shift) else float(shift)})
-    return PacketMatches(sim, groups, timing, carriers, carrier_of, measurements, iso, configs)
+    out = PacketMatches(sim, groups, timing, carriers, carrier_of, measurements, iso, configs)
+    if combine:
+        out.combined = combine_packets(iso, groups, sim.lag, min_rho=min_rho)
+        for cfg, y in zip(configs, out.combined.packets):
+            cfg["signal"] = y
+    return out
