@@ -135,6 +135,39 @@ def test_parity_over_sizes_and_gaps(gpu, T, noise, ni):
             assert ws[0] == 5 * T + 3 and we[-1] == n - 1
 
 
+TILE_GRID = 4096                     # kTileGrid in runs.hip: the blocks of the tile pass
+
+
+@pytest.fixture(scope="module")
+def three_tiles_a_block(T):
+    """2 * TILE_GRID + 2 tiles of low noise: tile 2 * TILE_GRID is block 0's third,
+    the one-element tile after it block 1's third (the element-wise path)."""
+    n = (2 * TILE_GRID + 1) * T + 1
+    return np.random.default_rng(32).random(n, dtype=np.float32) * np.float32(0.1)
+
+
+@pytest.mark.parametrize("variant", ["third_tile", "last_element", "equal_in_one_block"])
+def test_a_block_that_owns_three_tiles(gpu, T, three_tiles_a_block, variant):
+    """A block's slot rows are used a second time and its maximum accumulates
+    over three tiles: the info record and the list against the reference."""
+    a = three_tiles_a_block.copy()
+    n = len(a)
+    a[3 * T + 11:3 * T + 14] = 2.0
+    a[5000 * T + 7] = 3.0
+    if variant == "third_tile":
+        want = 2 * TILE_GRID * T + 100
+        a[want] = 5.0
+    elif variant == "last_element":
+        want = n - 1
+        a[want] = 5.0
+    else:                                # tiles 7 and 7 + TILE_GRID are one block's: the lower index wins
+        want = 7 * T + 5
+        a[want] = a[(7 + TILE_GRID) * T + 9] = 5.0
+    assert int(np.argmax(a)) == want
+    ws, _ = check(gpu, a, 1.0, 2)
+    assert len(ws) == (4 if variant == "equal_in_one_block" else 3)
+
+
 def test_first_start_and_last_end_do_not_depend_on_the_gap(gpu, T, noise):
     a = np.ascontiguousarray(noise[:3 * T + 5])
     m = mags(a)

@@ -19,7 +19,7 @@ SOURCES = ["psd.hip", "psd_traces.hip", "psd_segments.hip", "fir.hip", "isolate.
            "stream_ops.hip", "vector_build.hip", "peaks.hip", "runs.hip", "region.hip", "display.hip", "trace.hip", "chain.hip",
            "api_core.hip", "api_transform.hip", "api_spectrum.hip", "api_filter.hip", "api_xcorr.hip", "api_detect.hip",
            "api_vectors.hip", "api_match.hip", "api_combine.hip"]
-HEADERS = ["fft_engine.hpp", "os_common.hpp", "vsig_kernels.h", "combine_plan.hpp", "npabs.hpp", "dtype.hpp", "dbmath.hpp", "xcorr_epilogue.hpp", "psd_traces_run.hpp",
+HEADERS = ["fft_engine.hpp", "os_common.hpp", "vsig_kernels.h", "combine_plan.hpp", "npabs.hpp", "dtype.hpp", "block_ops.hpp", "dbmath.hpp", "xcorr_epilogue.hpp", "psd_traces_run.hpp",
            "vsig_ctx.hpp"]
 BUILD_ID_SOURCE = "api_core.hip"       # defines vsig_build_id(): the one unit compiled with the source hash
 API_HEADER = "vsig_ctx.hpp"            # included by the api_*.hip sources alone: an edit recompiles only those

@@ -17,8 +17,8 @@
 // allows); order statistics cost ceil(bits/8) histogram passes.
 #include <hip/hip_runtime.h>
 
+#include "block_ops.hpp"
 #include "dbmath.hpp"
-#include "dtype.hpp"
 
 namespace vsig {
 
@@ -101,6 +101,8 @@ __global__ __launch_bounds__(256) void thresh_reduce(const T* __restrict__ a, lo
     }
     mx = np_max(mx, v);
   }
+  // block_fold's order written out: as a value type of block_ops.hpp the
+  // partial costs three VGPRs (profiles/block_ops_ab.md)
   for (int off = 32; off > 0; off >>= 1) {
     cnt += __shfl_xor(cnt, off);
     const long long f2 = __shfl_xor(first, off), l2 = __shfl_xor(last, off);
@@ -136,52 +138,32 @@ template <class T> __device__ __forceinline__ double energy_of(const T* x, long 
   return sq_rn(mag(x[i]));
 }
 
-template <int BT>
-__device__ __forceinline__ double block_scan_excl(double v, double* total) {
-  // inclusive wave scan, then block
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  double s = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    const double o = __shfl_up(s, off);
-    if (lane >= off) s += o;
-  }
-  __shared__ double ws[BT / 64];
-  if (lane == 63) ws[w] = s;
-  __syncthreads();
-  double base = 0.0, tot = 0.0;
-  for (int q = 0; q < BT / 64; ++q) {
-    if (q < w) base += ws[q];
-    tot += ws[q];
-  }
-  __syncthreads();
-  *total = tot;
-  return base + s - v;
-}
-
 template <class T>
 __global__ __launch_bounds__(SCAN_T) void energy_tile_sums(const T* __restrict__ x, long long n,
                                                            double* __restrict__ sums) {
+  __shared__ double ws[SCAN_T / 64];
   const long long base = (long long)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_E;
   double acc = 0.0;
 #pragma unroll
   for (int e = 0; e < SCAN_E; ++e)
     if (base + e < n) acc += energy_of(x, base + e);
   double tot;
-  block_scan_excl<SCAN_T>(acc, &tot);
+  block_scan<SCAN_T / 64>(acc, ws, tot);
   if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
 __global__ __launch_bounds__(1024) void scan_sums(double* __restrict__ sums, long long nt) {
   // exclusive scan in place, one block, sequential chunks of 1024
+  __shared__ double ws[16];
   double carry = 0.0;
   for (long long c0 = 0; c0 < nt; c0 += 1024) {
     const long long i = c0 + threadIdx.x;
     const double v = i < nt ? sums[i] : 0.0;
     double tot;
-    const double ex = block_scan_excl<1024>(v, &tot);
+    const double ex = block_scan<16>(v, ws, tot);
     if (i < nt) sums[i] = carry + ex;
     carry += tot;
-    __syncthreads();
+    __syncthreads();                             // ws is written again by the next chunk
   }
 }
 
@@ -189,6 +171,7 @@ template <class T>
 __global__ __launch_bounds__(SCAN_T) void energy_prefix(const T* __restrict__ x, long long n,
                                                         const double* __restrict__ sums,
                                                         double* __restrict__ P) {
+  __shared__ double ws[SCAN_T / 64];
   const long long base = (long long)blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_E;
   double loc[SCAN_E];
   double acc = 0.0;
@@ -198,7 +181,7 @@ __global__ __launch_bounds__(SCAN_T) void energy_prefix(const T* __restrict__ x,
     loc[e] = acc;
   }
   double tot;
-  const double ex = block_scan_excl<SCAN_T>(acc, &tot) + sums[blockIdx.x];
+  const double ex = block_scan<SCAN_T / 64>(acc, ws, tot) + sums[blockIdx.x];
 #pragma unroll
   for (int e = 0; e < SCAN_E; ++e)
     if (base + e < n) P[base + e] = ex + loc[e];

@@ -12,8 +12,8 @@
 //     samples, A2 over the rest, and the same two sums of |p_k|^2 and |v|^2.
 //     Products are fp32 (contraction off, so p against itself gives |p|^2 and an
 //     imaginary part of exactly 0), widened to double and added in double in a
-//     fixed order: per thread in element order, the wave's lanes by a fixed
-//     butterfly, the waves in order.  The rotation is cis_rev on a phase formed
+//     fixed order: per thread in element order, then the block's threads by
+//     block_fold (block_ops.hpp).  The rotation is cis_rev on a phase formed
 //     in double, once per sample; f0 == 0 rotates nothing.  One fixed-slot
 //     partial per item; the items of one stretch of the reference are adjacent
 //     in the table, so it comes from L2 after its first read.
@@ -34,7 +34,7 @@
 // output sample of its group's members; neither depends on K, the other groups
 // or the grid.  Member loads are 8-byte loads (d_k shifts them by any number of
 // samples).  Every address comes from the plan's tables, never from a record.
-#include "vsig_kernels.h"
+#include "block_ops.hpp"
 
 namespace vsig {
 
@@ -75,7 +75,8 @@ __global__ __launch_bounds__(CT) void combine_estimate_kernel(
       r[i] = v[mb.lo + q];                     // in [0, L_g): lo + n <= L_g
     }
   }
-  double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  Sums<8> acc{{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
+  double* s = acc.s;
 #pragma unroll
   for (int i = 0; i < CV; ++i) {
     const long long q = c0 + threadIdx.x + i * CT;
@@ -95,26 +96,10 @@ __global__ __launch_bounds__(CT) void combine_estimate_kernel(
     s[6] += first ? ev : 0.0;
     s[7] += rest ? ev : 0.0;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s[k] += __shfl_xor(s[k], off);
-  }
-  __shared__ double sw[8][CW];
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) sw[k][threadIdx.x >> 6] = s[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      t[k] = sw[k][0];
-      for (int w = 1; w < CW; ++w) t[k] += sw[k][w];
-    }
-    parts[mb.slot + it.chunk] = CombinePartial{t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]};
-  }
+  __shared__ Sums<8> slots[CW];
+  block_fold<CW>(acc, slots);
+  if (threadIdx.x == 0)
+    parts[mb.slot + it.chunk] = CombinePartial{s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7]};
 }
 
 __global__ __launch_bounds__(CT) void combine_finalize_kernel(

@@ -1,9 +1,9 @@
 // The element-type layer of the kernels that take "an array of dtype VSIG_*"
 // and work on |a| (gfx950): numpy's |a| of one element, the two compare rules
 // of their reductions, 16-byte packs, and the switch from a dtype code to the
-// element type.  Included by os_common.hpp (and through it by reduce.hip,
-// refine.hip, psd_traces.hip), peaks.hip, trace.hip, analysis.hip, display.hip
-// and the C-ABI layer (vsig_ctx.hpp).
+// element type.  Included by block_ops.hpp (and through it by os_common.hpp
+// and its includers, peaks.hip, runs.hip, region.hip, combine.hip,
+// analysis.hip, trace.hip), display.hip and the C-ABI layer (vsig_ctx.hpp).
 #pragma once
 #include "npabs.hpp"
 #include "vsig_kernels.h"

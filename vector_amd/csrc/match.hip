@@ -8,8 +8,8 @@
 // the next transform's operand layout).
 //   match_spectra_kernel  one block per packet: P_k = FFT_N(p_k zero-padded) in
 //     natural order into row k of the plan's K x N workspace; E_k as a double
-//     sum of the fp32 squares (per thread in element order, the wave's lanes by
-//     a fixed butterfly, the waves in order); the diagonal record (a, a).
+//     sum of the fp32 squares (per thread in element order, then block_fold,
+//     block_ops.hpp); the diagonal record (a, a).
 //   match_pairs_kernel    a unit is (a, b0, nb): packet a against b0 .. b0 + nb
 //     - 1, all > a.  The block loads P_a / N into registers once per unit (it
 //     transforms nothing for a) and for every b forms conj(P_a / N) P_b, runs
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(P::TF) void match_spectra_kernel(
     int* __restrict__ lag, const float2* __restrict__ tw) {
   static_assert(P::R[0] == P::RL, "the pair kernel needs a palindromic plan");
   __shared__ __attribute__((aligned(16))) float2 lds[lds_size<P>()];
-  __shared__ double wsum[P::TF / 64];
+  __shared__ Sums<1> wsum[P::TF / 64];
   const int t = threadIdx.x;
   const int k = blockIdx.x;
   const long long o = offsets[k];
@@ -47,25 +47,23 @@ __global__ __launch_bounds__(P::TF) void match_spectra_kernel(
   load_anchors<P>(wa, tw, t);
   float2 X[P::E];
   load_segment<P>(X, packed + o, 0, L, t);        // L < N: the bounds-tested path, zero fill
-  double s = 0.0;
+  Sums<1> s{{0.0}};
 #pragma unroll
-  for (int e = 0; e < P::E; ++e) s += (double)(X[e].x * X[e].x + X[e].y * X[e].y);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  if ((t & 63) == 0) wsum[t >> 6] = s;
-  fft_frame_anch<P>(X, lds, wa, t);
-  float2* __restrict__ Wk = W + (long long)k * P::N;
-#pragma unroll
-  for (int e = 0; e < P::E; ++e) Wk[out_index<P>(t, e)] = X[e];
-  __syncthreads();
+  for (int e = 0; e < P::E; ++e) s.s[0] += (double)(X[e].x * X[e].x + X[e].y * X[e].y);
+  // before the transform: behind it the fold's value would stay live across
+  // it and double the kernel's VGPRs (profiles/block_ops_ab.md)
+  block_fold<P::TF / 64>(s, wsum);
   if (t == 0) {
-    double E = 0.0;
-    for (int w = 0; w < P::TF / 64; ++w) E += wsum[w];
+    const double E = s.s[0];
     energy[k] = E;
     const long long d = (long long)k * K + k;
     peak[d] = isfinite(E) ? (float)E : __builtin_nanf("");
     lag[d] = 0;
   }
+  fft_frame_anch<P>(X, lds, wa, t);
+  float2* __restrict__ Wk = W + (long long)k * P::N;
+#pragma unroll
+  for (int e = 0; e < P::E; ++e) Wk[out_index<P>(t, e)] = X[e];
 }
 
 template <class P>
@@ -117,12 +115,7 @@ __global__ __launch_bounds__(P::TF, match_waves_per_eu<P>()) void match_pairs_ke
         ml = take ? l : ml;
       }
       // lane 63 ends with the wave's (max, smallest lag on ties)
-      peak_dpp_step<0xb1, 0xf>(m, ml, s1, s2, false);
-      peak_dpp_step<0x4e, 0xf>(m, ml, s1, s2, false);
-      peak_dpp_step<0x124, 0xf>(m, ml, s1, s2, false);
-      peak_dpp_step<0x128, 0xf>(m, ml, s1, s2, false);
-      peak_dpp_step<0x142, 0xa>(m, ml, s1, s2, false);
-      peak_dpp_step<0x143, 0xc>(m, ml, s1, s2, false);
+      wave_peak_dpp(m, ml, s1, s2, false);
       if ((t & 63) == 63) { red_m[t >> 6] = m; red_l[t >> 6] = ml; }
       __syncthreads();        // the next transform's barriers keep the next writes behind this read
       if (t == 0) {

@@ -1,10 +1,12 @@
 // Shared pieces of the overlap-save / streaming kernels (gfx950): launch
-// geometry, segment loads, DPP wave reductions of |c| partials, plan switches.
-// Included by psd.hip, fir.hip, xcorr.hip, reduce.hip (one translation unit
-// each, compiled in parallel; every kernel is launched from its own TU).
+// geometry, segment loads, the block partial and the DPP wave partials of the
+// |c| reductions, plan switches.  Included by psd.hip, psd_traces.hip,
+// psd_segments.hip, fir.hip, isolate.hip, xcorr.hip, xcorr_bank.hip, match.hip,
+// reduce.hip, refine.hip, bigfft.hip (one translation unit each, compiled in
+// parallel; every kernel is launched from its own TU).
 #pragma once
 #include "fft_engine.hpp"
-#include "dtype.hpp"
+#include "block_ops.hpp"
 
 namespace vsig {
 
@@ -160,30 +162,15 @@ __device__ __forceinline__ void load_segment_mix(float2* v, const float2* __rest
 
 // ---------------------------------------------------------------------------
 // Block partial of a |c| reduction: max |c|^2 (lowest index on ties),
-// sum |c|, sum |c|^2 (betterd: dtype.hpp).
+// sum |c|, sum |c|^2, folded in block_ops.hpp's order.
 // ---------------------------------------------------------------------------
 template <int BT>
 __device__ __forceinline__ void block_partial(double m, long long mi, double s1, double s2,
                                               PeakPartial* out) {
-  // wave reduce (64 lanes)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double om = __shfl_xor(m, off);
-    const long long oi = __shfl_xor(mi, off);
-    betterd(m, mi, om, oi);
-    s1 += __shfl_xor(s1, off);
-    s2 += __shfl_xor(s2, off);
-  }
-  constexpr int NW = BT / 64;
-  __shared__ double sm[NW], ss1[NW], ss2[NW];
-  __shared__ long long si[NW];
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  if (l == 0) { sm[w] = m; si[w] = mi; ss1[w] = s1; ss2[w] = s2; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int q = 1; q < NW; ++q) { betterd(m, mi, sm[q], si[q]); s1 += ss1[q]; s2 += ss2[q]; }
-    out->max2 = m; out->idx = mi; out->sum_abs = s1; out->sum_abs2 = s2;
-  }
+  __shared__ FirstMaxSums<2> slots[BT / 64];
+  FirstMaxSums<2> v{{m, mi}, {{s1, s2}}};
+  block_fold<BT / 64>(v, slots);
+  if (threadIdx.x == 0) { out->max2 = v.m; out->idx = v.i; out->sum_abs = v.s[0]; out->sum_abs2 = v.s[1]; }
 }
 
 // Partials of the correlators: float |c|^2 / int block-local index / float
@@ -209,18 +196,22 @@ __device__ __forceinline__ void peak_dpp_step(float& m, int& mi, float& s1, floa
   s2 += dpp_f<CTRL, RM>(s2);
 }
 
-// One partial per wave (no block barrier at the block's tail): lane 63 holds
-// the wave's result after the DPP steps and writes it.
-__device__ __forceinline__ void wave_partial_f(float m, int mi, float s1, float s2, bool rev,
-                                               long long ob, long long nout, PeakPartial* out) {
-  // rocPRIM-style wave64 reduction: quad xor 1, 2; row_ror 4, 8; row_bcast 15, 31
-  // -> lane 63 holds the wave's result (rows not feeding it hold garbage).
+// rocPRIM-style wave64 reduction: quad xor 1, 2; row_ror 4, 8; row_bcast 15, 31
+// -> lane 63 holds the wave's result (rows not feeding it hold garbage).
+__device__ __forceinline__ void wave_peak_dpp(float& m, int& mi, float& s1, float& s2, bool rev) {
   peak_dpp_step<0xb1, 0xf>(m, mi, s1, s2, rev);
   peak_dpp_step<0x4e, 0xf>(m, mi, s1, s2, rev);
   peak_dpp_step<0x124, 0xf>(m, mi, s1, s2, rev);
   peak_dpp_step<0x128, 0xf>(m, mi, s1, s2, rev);
   peak_dpp_step<0x142, 0xa>(m, mi, s1, s2, rev);
   peak_dpp_step<0x143, 0xc>(m, mi, s1, s2, rev);
+}
+
+// One partial per wave (no block barrier at the block's tail): lane 63 holds
+// the wave's result after the DPP steps and writes it.
+__device__ __forceinline__ void wave_partial_f(float m, int mi, float s1, float s2, bool rev,
+                                               long long ob, long long nout, PeakPartial* out) {
+  wave_peak_dpp(m, mi, s1, s2, rev);
   if ((threadIdx.x & 63) == 63) {
     long long gi = ob + mi;
     if (rev) gi = nout - 1 - gi;

@@ -35,7 +35,7 @@
 // nothing but NaN has maximum -1 at its first index).
 #include <climits>
 
-#include "dtype.hpp"
+#include "block_ops.hpp"
 
 namespace vsig {
 
@@ -53,9 +53,7 @@ __global__ __launch_bounds__(PT) void peaks_tile(const T* __restrict__ a, long l
                                                  PeakPartial* __restrict__ tab,
                                                  PeakPartial* __restrict__ bpart) {
   constexpr int EPV = 16 / sizeof(T), NV = kPeaksTile / (PT * EPV);
-  __shared__ double sm[2][PW];
-  __shared__ long long si[2][PW];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __shared__ FirstMax slots[2][PW];          // alternate between tiles: one barrier a tile is enough
   int par = 0;
   double bm = -2.0;                          // thread 0: the block's tiles so far
   long long bi = LLONG_MAX;
@@ -80,22 +78,14 @@ __global__ __launch_bounds__(PT) void peaks_tile(const T* __restrict__ a, long l
         if (g < n) betterd(m, mi, (double)mag(a[g]), g);
       }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const double om = __shfl_xor(m, off);
-      const long long oi = __shfl_xor(mi, off);
-      betterd(m, mi, om, oi);
-    }
-    // sm / si alternate between tiles: one barrier a tile is enough
-    if (lane == 0) { sm[par][w] = m; si[par][w] = mi; }
-    __syncthreads();
+    FirstMax v{m, mi};
+    block_fold<PW>(v, slots[par]);
     if (threadIdx.x == 0) {
-      for (int q = 1; q < PW; ++q) betterd(m, mi, sm[par][q], si[par][q]);
-      if (mi == LLONG_MAX) mi = base;        // nothing but NaN
+      if (v.i == LLONG_MAX) v.i = base;      // nothing but NaN
       PeakPartial r;
-      r.max2 = m; r.idx = mi; r.sum_abs = 0.0; r.sum_abs2 = 0.0;
+      r.max2 = v.m; r.idx = v.i; r.sum_abs = 0.0; r.sum_abs2 = 0.0;
       tab[tile] = r;
-      betterd(bm, bi, m, mi);
+      betterd(bm, bi, v.m, v.i);
     }
   }
   if (threadIdx.x == 0) {                    // every block has at least one tile
@@ -269,26 +259,13 @@ __global__ __launch_bounds__(1024) void peaks_scan(long long* __restrict__ goff,
                                                    const PeakPartial* __restrict__ rec, double thr,
                                                    int relative, PeaksInfo* __restrict__ info) {
   __shared__ long long ws[16];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const long long chunk = (ng + 1023) / 1024;
   const long long lo = threadIdx.x * chunk;
   const long long hi = lo + chunk < ng ? lo + chunk : ng;
   long long s = 0;
   for (long long i = lo; i < hi; ++i) s += goff[i];
-  long long x = s;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const long long y = __shfl_up(x, off);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) ws[w] = x;
-  __syncthreads();
-  long long before = 0, total = 0;
-  for (int q = 0; q < 16; ++q) {
-    if (q < w) before += ws[q];
-    total += ws[q];
-  }
-  long long run = before + x - s;
+  long long total;
+  long long run = block_scan<16>(s, ws, total);
   for (long long i = lo; i < hi; ++i) {
     const long long v = goff[i];
     goff[i] = run;

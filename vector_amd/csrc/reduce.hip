@@ -39,6 +39,8 @@ __global__ __launch_bounds__(1024) void peak_first_nan(const T* __restrict__ a, 
     const double v = (double)mag(a[i]);
     if (v != v) { first = i; break; }
   }
+  // block_fold's order written out: as a value type of block_ops.hpp the index
+  // costs the real instantiations a VGPR (profiles/block_ops_ab.md)
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const long long o = __shfl_xor(first, off);

@@ -16,8 +16,7 @@
 // The grid is a function of n alone and nothing is accumulated across blocks
 // by atomics, so the sums have the same bits on every run over the same
 // operands.  a == b is fine: both are only read.
-#include "npabs.hpp"
-#include "vsig_kernels.h"
+#include "block_ops.hpp"
 
 namespace vsig {
 
@@ -25,8 +24,9 @@ namespace {
 
 constexpr int RT = 256;                      // threads per block
 constexpr int RV = 2;                        // samples per lane and trip (one 16-byte load an operand)
+constexpr int RW = RT / 64;
 
-struct RegionPartial { double s[3]; };
+using RegionPartial = Sums<3>;               // S0, S1, S2 of a block, folded in block_ops.hpp's order
 static_assert(sizeof(RegionPartial) == 24, "three doubles per block");
 
 #pragma clang fp contract(off)
@@ -49,40 +49,14 @@ __device__ __forceinline__ void acc4(double* s, const float4& u, const float4& v
   acc(s, u.z, u.w, v.z, v.w);
 }
 
-// Wave sums by xor shuffles, then thread 0 adds the waves' in order.
-template <int BT>
-__device__ __forceinline__ void block_sums(double* s, RegionPartial* out) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s[k] += __shfl_xor(s[k], off);
-  }
-  constexpr int NW = BT / 64;
-  __shared__ double sw[3][NW];
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  if (l == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sw[k][w] = s[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    RegionPartial r;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      double t = s[k];
-      for (int q = 1; q < NW; ++q) t += sw[k][q];
-      r.s[k] = t;
-    }
-    *out = r;
-  }
-}
-
 // VEC: a + head and b + head are 16-byte aligned (head = 0 or 1).
 template <bool VEC>
 __global__ __launch_bounds__(RT) void region_power(const float2* __restrict__ a,
                                                    const float2* __restrict__ b, long long n,
                                                    int head, RegionPartial* __restrict__ parts) {
-  double s[3] = {0.0, 0.0, 0.0};
+  __shared__ RegionPartial slots[RW];
+  RegionPartial part{{0.0, 0.0, 0.0}};
+  double* s = part.s;
   const long long stride = (long long)gridDim.x * RT;
   const long long t0 = (long long)blockIdx.x * RT + threadIdx.x;
   if (VEC) {
@@ -107,21 +81,20 @@ __global__ __launch_bounds__(RT) void region_power(const float2* __restrict__ a,
       acc(s, u.x, u.y, v.x, v.y);
     }
   }
-  block_sums<RT>(s, parts + blockIdx.x);
+  block_fold<RW>(part, slots);
+  if (threadIdx.x == 0) parts[blockIdx.x] = part;
 }
 
 __global__ __launch_bounds__(RT) void region_finalize(const RegionPartial* __restrict__ parts,
                                                       int nparts, double* __restrict__ out) {
-  double s[3] = {0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < nparts; i += RT) {
-    const RegionPartial p = parts[i];
+  __shared__ RegionPartial slots[RW];
+  RegionPartial part{{0.0, 0.0, 0.0}};
+  for (int i = threadIdx.x; i < nparts; i += RT) part.merge(parts[i]);
+  block_fold<RW>(part, slots);
+  if (threadIdx.x == 0) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) s[k] += p.s[k];
+    for (int k = 0; k < 3; ++k) out[k] = part.s[k];
   }
-  __shared__ RegionPartial tot;
-  block_sums<RT>(s, &tot);
-  __syncthreads();
-  if (threadIdx.x < 3) out[threadIdx.x] = tot.s[threadIdx.x];
 }
 
 }  // namespace

@@ -43,7 +43,7 @@
 // masked: such arrays are outside the contract, the writes stay in bounds).
 #include <climits>
 
-#include "dtype.hpp"
+#include "block_ops.hpp"
 
 namespace vsig {
 
@@ -57,10 +57,14 @@ constexpr int RWORDS = kRunsTile / 64;       // mask words per tile
 constexpr int RB = RG * RWORDS;              // threads of runs_words: one per mask word
 constexpr int RBW = RB / 64;
 static_assert(RB == 1024 && RWORDS == 32, "runs_words maps thread >> 5 to the tile, & 31 to the word");
+// a mask word has at most 32 starts and 32 ends, a block at most 32 RB of either:
+// runs_words scans both counts as the halves of one 64-bit word
+static_assert(32LL * RB < (1LL << 31), "a block's start and end counts each fit a 32-bit half");
 constexpr long long kNone = 1LL << 60;       // no masked index: p = -kNone, q = +kNone
 
 struct RunTile { double max; long long idx; double min, sum; };
 struct RunGroup { double max; long long idx; double sum; };   // a group's tiles together
+using StatFold = FirstMaxSums<1>;   // {max, first index, sum} on its way into a group or run record
 
 // 0: nothing masked, 1: everything masked, 2: mixed
 __device__ __forceinline__ int tile_class(double mx, double mn, double thr) {
@@ -160,6 +164,8 @@ __global__ __launch_bounds__(RT) void runs_tile(const T* __restrict__ a, long lo
         }
       }
     }
+    // block_fold's order written out: as a value type of block_ops.hpp the four
+    // fields cost the unaligned instantiations a VGPR (profiles/block_ops_ab.md)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       const double om = __shfl_xor(m, off);
@@ -225,7 +231,7 @@ __device__ __forceinline__ unsigned long long word_of(const RunsArgs& A, long lo
 // mixed tiles are read again here.
 template <class T, bool BITS>
 __global__ __launch_bounds__(RT) void runs_mask(RunsArgs A) {
-  __shared__ long long sf[RW], sl[RW], sc[RW];
+  __shared__ Span slots[RW];
   __shared__ int scls[RG];
   const T* a = static_cast<const T*>(A.a);
   const double thr = thr_of(A);
@@ -235,35 +241,28 @@ __global__ __launch_bounds__(RT) void runs_mask(RunsArgs A) {
     // the group's tiles side by side: their classes, and {max, first index,
     // sum} of the whole group for the statistics of long runs
     const long long t = t0 + threadIdx.x;
-    double m = -2.0, s = 0.0;
-    long long mi = LLONG_MAX;
+    StatFold v{{-2.0, LLONG_MAX}, {{0.0}}};
     int cls = 0;
     if (t < A.ntiles) {
       const RunTile e = A.tab[t];
-      m = e.max; mi = e.idx; s = e.sum;
+      v.m = e.max; v.i = e.idx; v.s[0] = e.sum;
       cls = tile_class(e.max, e.min, thr);
     }
     scls[threadIdx.x] = cls;
-#pragma unroll
-    for (int off = RG / 2; off > 0; off >>= 1) {             // lanes 0 .. RG-1 among themselves
-      const double om = __shfl_xor(m, off);
-      const long long oi = __shfl_xor(mi, off);
-      betterd(m, mi, om, oi);
-      s += __shfl_xor(s, off);
-    }
+    wave_fold<RG>(v);                            // lanes 0 .. RG-1 among themselves
     if (threadIdx.x == 0) {
       RunGroup r;
-      r.max = m; r.idx = mi; r.sum = s;
+      r.max = v.m; r.idx = v.i; r.sum = v.s[0];
       A.gtab[blockIdx.x] = r;
     }
   }
   __syncthreads();
-  long long f = kNone, l = -kNone, c = 0;      // this thread's mask words so far
+  Span sp{kNone, -kNone, 0};                   // this thread's mask words so far
   auto take = [&](unsigned long long B, long long b0) {
     if (B) {
-      f = lmin(f, b0 + __builtin_ctzll(B));
-      l = lmax(l, b0 + 63 - __builtin_clzll(B));
-      c += __popcll(B);
+      sp.first = lmin(sp.first, b0 + __builtin_ctzll(B));
+      sp.last = lmax(sp.last, b0 + 63 - __builtin_clzll(B));
+      sp.count += __popcll(B);
     }
   };
   if (!BITS) {
@@ -285,17 +284,9 @@ __global__ __launch_bounds__(RT) void runs_mask(RunsArgs A) {
     const int word = i % RWORDS;
     if (t < A.ntiles) take(word_of(A, t, word, scls[i / RWORDS]), t * kRunsTile + 64 * word);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    f = lmin(f, __shfl_xor(f, off));
-    l = lmax(l, __shfl_xor(l, off));
-    c += __shfl_xor(c, off);
-  }
-  if (lane == 0) { sf[w] = f; sl[w] = l; sc[w] = c; }
-  __syncthreads();
+  block_fold<RW>(sp, slots);
   if (threadIdx.x == 0) {
-    for (int q = 1; q < RW; ++q) { f = lmin(f, sf[q]); l = lmax(l, sl[q]); c += sc[q]; }
-    A.gfirst[blockIdx.x] = f; A.glast[blockIdx.x] = l; A.gcov[blockIdx.x] = c;
+    A.gfirst[blockIdx.x] = sp.first; A.glast[blockIdx.x] = sp.last; A.gcov[blockIdx.x] = sp.count;
   }
 }
 
@@ -306,28 +297,13 @@ __global__ __launch_bounds__(1024) void runs_scan_edges(const long long* __restr
                                                         const long long* __restrict__ glast, long long ng,
                                                         long long* __restrict__ gp, long long* __restrict__ gq) {
   __shared__ long long wl[16], wf[16];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const long long chunk = (ng + 1023) / 1024;
   const long long lo = lmin(threadIdx.x * chunk, ng);
   const long long hi = lmin(lo + chunk, ng);
   long long x = -kNone, y = kNone;
   for (long long i = lo; i < hi; ++i) { x = lmax(x, glast[i]); y = lmin(y, gfirst[i]); }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const long long ux = __shfl_up(x, off), dy = __shfl_down(y, off);
-    if (lane >= off) x = lmax(x, ux);
-    if (lane + off < 64) y = lmin(y, dy);
-  }
-  if (lane == 63) wl[w] = x;
-  if (lane == 0) wf[w] = y;
-  __syncthreads();
-  long long p = __shfl_up(x, 1), q = __shfl_down(y, 1);
-  if (lane == 0) p = -kNone;
-  if (lane == 63) q = kNone;
-  for (int k = 0; k < 16; ++k) {
-    if (k < w) p = lmax(p, wl[k]);
-    if (k > w) q = lmin(q, wf[k]);
-  }
+  long long p, q;
+  block_scan_edges<16>(x, y, kNone, wl, wf, p, q);
   for (long long i = lo; i < hi; ++i) { gp[i] = p; p = lmax(p, glast[i]); }
   for (long long i = hi - 1; i >= lo; --i) { gq[i] = q; q = lmin(q, gfirst[i]); }
 }
@@ -359,11 +335,9 @@ __device__ __forceinline__ void word_ends(unsigned long long B, long long b0, lo
 
 template <bool EMIT>
 __global__ __launch_bounds__(RB) void runs_words(RunsArgs A) {
-  __shared__ long long wl[RBW], wf[RBW];
-  __shared__ int ws[RBW], we[RBW];
+  __shared__ long long wl[RBW], wf[RBW], wc[RBW];
   __shared__ unsigned short live[RB];
   __shared__ int nlive;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int word = threadIdx.x & 31;
   const double thr = thr_of(A);
   // The block owns a contiguous chunk of groups, at most RB of them (the
@@ -395,26 +369,11 @@ __global__ __launch_bounds__(RB) void runs_words(RunsArgs A) {
     unsigned long long B = 0;
     if (t < A.ntiles) B = word_of(A, t, word, tile_class(A.tab[t].max, A.tab[t].min, thr));
     // p: the last set bit of the words before this one; q: the first of those after it
-    long long x = B ? b0 + 63 - __builtin_clzll(B) : -kNone;
-    long long y = B ? b0 + __builtin_ctzll(B) : kNone;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const long long ux = __shfl_up(x, off), dy = __shfl_down(y, off);
-      if (lane >= off) x = lmax(x, ux);
-      if (lane + off < 64) y = lmin(y, dy);
-    }
-    if (lane == 63) wl[w] = x;
-    if (lane == 0) wf[w] = y;
-    __syncthreads();
-    long long p = __shfl_up(x, 1), q = __shfl_down(y, 1);
-    if (lane == 0) p = -kNone;
-    if (lane == 63) q = kNone;
+    long long p, q;
+    block_scan_edges<RBW>(B ? b0 + 63 - __builtin_clzll(B) : -kNone, B ? b0 + __builtin_ctzll(B) : kNone, kNone,
+                          wl, wf, p, q);
     p = lmax(p, A.gp[g]);
     q = lmin(q, A.gq[g]);
-    for (int k = 0; k < RBW; ++k) {
-      if (k < w) p = lmax(p, wl[k]);
-      if (k > w) q = lmin(q, wf[k]);
-    }
     int cs = 0, ce = 0;
     if (A.gap1 == 1) {
       // max_gap = 0: every stretch of ones opens and closes a run, but for
@@ -426,49 +385,20 @@ __global__ __launch_bounds__(RB) void runs_words(RunsArgs A) {
       word_starts(B, b0, p, A.gap1, [&](long long) { ++cs; });
       word_ends(B, b0, q, A.gap1, [&](long long) { ++ce; });
     }
-    // the counts of the threads up to this one (a word has at most 32 of either)
-    int xs = cs, xe = ce;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int us = __shfl_up(xs, off), ue = __shfl_up(xe, off);
-      if (lane >= off) { xs += us; xe += ue; }
-    }
-    if (lane == 63) { ws[w] = xs; we[w] = xe; }
-    __syncthreads();
+    // the counts of the threads before this one, both in one scan: starts in
+    // the low half, ends in the high (a word has at most 32 of either, a block
+    // 2^15: neither half carries)
+    long long tot;
+    const long long before = block_scan<RBW>((long long)cs | ((long long)ce << 32), wc, tot);
     if (!EMIT) {
-      if (threadIdx.x == 0) {
-        long long ts = 0, te = 0;
-        for (int k = 0; k < RBW; ++k) { ts += ws[k]; te += we[k]; }
-        A.gcs[g] = ts; A.gce[g] = te;
-      }
+      if (threadIdx.x == 0) { A.gcs[g] = tot & 0xffffffffll; A.gce[g] = tot >> 32; }
     } else {
-      long long ks = A.gcs[g] + (xs - cs), ke = A.gce[g] + (xe - ce);
-      for (int k = 0; k < w; ++k) { ks += ws[k]; ke += we[k]; }
+      long long ks = A.gcs[g] + (before & 0xffffffffll), ke = A.gce[g] + (before >> 32);
       word_starts(B, b0, p, A.gap1, [&](long long i) { if (ks < A.cap) A.out[ks].start = i; ++ks; });
       word_ends(B, b0, q, A.gap1, [&](long long i) { if (ke < A.cap) A.out[ke].end = i; ++ke; });
     }
     __syncthreads();                             // the LDS slots are reused by the block's next group
   }
-}
-
-// exclusive prefix of s over the block's threads (and the block's total); ws: 16 slots
-__device__ __forceinline__ long long block_prefix(long long s, long long* ws, long long* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  long long x = s;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const long long y = __shfl_up(x, off);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) ws[w] = x;
-  __syncthreads();
-  long long before = 0, tot = 0;
-  for (int q = 0; q < 16; ++q) {
-    if (q < w) before += ws[q];
-    tot += ws[q];
-  }
-  *total = tot;
-  return before + x - s;
 }
 
 // One block: exclusive scan in place of the ng per-group start and end
@@ -484,9 +414,9 @@ __global__ __launch_bounds__(1024) void runs_scan_counts(long long* __restrict__
   long long s = 0, e = 0, c = 0;
   for (long long i = lo; i < hi; ++i) { s += gcs[i]; e += gce[i]; c += gcov[i]; }
   long long ts, te, tc;
-  long long rs = block_prefix(s, w0, &ts);
-  long long re = block_prefix(e, w1, &te);
-  (void)block_prefix(c, w2, &tc);
+  long long rs = block_scan<16>(s, w0, ts);
+  long long re = block_scan<16>(e, w1, te);
+  (void)block_scan<16>(c, w2, tc);
   for (long long i = lo; i < hi; ++i) {
     const long long vs = gcs[i], ve = gce[i];
     gcs[i] = rs; gce[i] = re;
@@ -507,10 +437,8 @@ constexpr int kStatsGrid = 2048;
 
 template <class T>
 __global__ __launch_bounds__(RT) void runs_stats(RunsArgs A) {
-  __shared__ double smx[2][RW], ssum[2][RW];
-  __shared__ long long si[2][RW];
+  __shared__ StatFold slots[2][RW];          // alternate between records: one barrier a record is enough
   const T* a = static_cast<const T*>(A.a);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const long long cnt = A.info->count;
   const long long kmax = cnt < A.cap ? cnt : A.cap;
   int par = 0;
@@ -554,22 +482,11 @@ __global__ __launch_bounds__(RT) void runs_stats(RunsArgs A) {
         sum += v;
       }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const double om = __shfl_xor(m, off);
-      const long long oi = __shfl_xor(mi, off);
-      betterd(m, mi, om, oi);
-      sum += __shfl_xor(sum, off);
-    }
-    if (lane == 0) { smx[par][w] = m; si[par][w] = mi; ssum[par][w] = sum; }
-    __syncthreads();
+    StatFold v{{m, mi}, {{sum}}};
+    block_fold<RW>(v, slots[par]);
     if (threadIdx.x == 0) {
-      for (int q = 1; q < RW; ++q) {
-        betterd(m, mi, smx[par][q], si[par][q]);
-        sum += ssum[par][q];
-      }
-      if (mi == LLONG_MAX) mi = s;             // nothing but NaN
-      A.out[k].argmax = mi; A.out[k].max = m; A.out[k].sum = sum;
+      if (v.i == LLONG_MAX) v.i = s;           // nothing but NaN
+      A.out[k].argmax = v.i; A.out[k].max = v.m; A.out[k].sum = v.s[0];
     }
   }
 }

@@ -35,8 +35,8 @@
 // pair, so info over an array with NaN holds the extrema of the rest.
 #include <climits>
 
+#include "block_ops.hpp"
 #include "dbmath.hpp"
-#include "dtype.hpp"
 
 namespace vsig {
 
@@ -87,15 +87,9 @@ struct Ext {
     take_min((R)r.mn, r.pmn);
     nan |= (int)r.nan;
   }
-  __device__ __forceinline__ void wave() {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      Ext o;
-      o.mx = __shfl_xor(mx, off); o.mn = __shfl_xor(mn, off);
-      o.pmx = __shfl_xor(pmx, off); o.pmn = __shfl_xor(pmn, off);
-      o.nan = __shfl_xor(nan, off);
-      merge(o);
-    }
+  __device__ __forceinline__ Ext shfl_xor(int off) const {
+    return {__shfl_xor(mx, off), __shfl_xor(mn, off), __shfl_xor(pmx, off), __shfl_xor(pmn, off),
+            __shfl_xor(nan, off)};
   }
   __device__ __forceinline__ TraceRec rec() const {
     TraceRec r;
@@ -104,18 +98,12 @@ struct Ext {
   }
 };
 
-// The block's lanes -> one record, by thread 0 (waves merged in order).
+// The block's lanes -> one record, by thread 0.
 template <class R>
 __device__ __forceinline__ void block_record(Ext<R> e, TraceRec* out) {
-  __shared__ TraceRec sw[TW];
-  e.wave();
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) sw[w] = e.rec();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int q = 1; q < TW; ++q) e.merge(sw[q]);
-    *out = e.rec();
-  }
+  __shared__ Ext<R> slots[TW];
+  block_fold<TW>(e, slots);
+  if (threadIdx.x == 0) *out = e.rec();
 }
 
 struct TraceArgs {
@@ -262,7 +250,7 @@ __global__ __launch_bounds__(TT) void trace_merge(TraceArgs A) {
   Ext<R> e;
   e.init();
   for (long long j = lane; j < A.cpc; j += 64) e.merge(A.recs[c * A.cpc + j]);
-  e.wave();
+  wave_fold(e);
   if (lane == 0) {
     R* emin = static_cast<R*>(A.env_min);
     R* emax = static_cast<R*>(A.env_max);
